@@ -3,7 +3,12 @@
 FOCAL loss head -> backward -> fused AdamW), BASELINE.json's metric.
 
   python bench.py [--gpus N --steps K --warmup W] [--model SW_Transformer|DeepSense] [--batch 256] [--dtype bf16|fp32]
+                  [--full] [--dump-outputs DIR]
   N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the line; --full adds the roofline, the secondary workloads, the CPU
+baseline and the dp diagnostics after the headline.  --dump-outputs writes what the timed step computes from the seeded initial
+state (InitialState, dump_outputs).
 
 Workload (config.workload): BASELINE.json configs[2] at N=1 -- SW_Transformer + FOCAL, bf16 operands, 256 synthetic
 MOD-shaped 2-modality windows per GPU (audio [1,10,1600] @ 8 kHz, seismic [1,10,20] @ 100 Hz, N(0,1), 64
@@ -26,6 +31,7 @@ for p in (ROOT, os.path.join(ROOT, "focal_amd", "src")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -34,6 +40,8 @@ FLOP_PER_WINDOW = {"SW_Transformer/MOD": 4.376e9, "DeepSense/MOD": 0.809e9}  # S
 HBM_PEAK_GBS = 8000.0
 MFMA_BF16_PEAK_TF = 2500.0
 MFMA_F32_PEAK_TF = 157.3
+DUMP_MAX_ELEMS = 1 << 22  # --dump-outputs: per array, 16 MiB of float32
+DROPOUT_SEED, VIEW_SEED = 1234, 4321  # the device RNG words (the library draws them from os.urandom by default): same masks every run
 
 
 def parse():
@@ -62,6 +70,13 @@ def parse():
                         "the round-4 form, draws and warp tables on the host, eagerly before every replay, inside the timed region")
     p.add_argument("--trace-dump", default=None, help="write the library's launch trace of 5 eager steps (per-instance medians, both trace modes) to this JSON file and exit")
     p.add_argument("--no-roofline", action="store_true", help="profiling runs: skip the dominant-kernel timing loop (the JSON line then has roofline null)")
+    p.add_argument("--full", action="store_true", help="after the headline also measure what a plain run leaves out: the in-step roofline, the "
+                   "DeepSense / HAR4 lines, the CPU baseline and (N > 1) the dp diagnostics.  Without it those keys of the JSON line are null")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps put the training state back to its seeded initial values, run the timed step once more "
+                        "and write what it computed as DIR/<name>.npy: loss, loss_terms (float64) and gradients (float32, flattened in "
+                        f"named_parameters order; a fixed seeded sample where larger than {DUMP_MAX_ELEMS} elements).  The "
+                        "arrays depend on the arguments only, not on how many steps ran before")
     return p.parse_args()
 
 
@@ -848,8 +863,8 @@ def dp_diagnostics(a, step, world, device, graphed):
 
 def secondary_workloads(a, device):
     """BASELINE configs[1] (DeepSense, MOD) and the per-GPU workload of configs[4] (SW_Transformer, 4-modality HAR4) timed by the same
-    process right after the headline, the same way (captured step, 10 warm-up + 20 timed steps, loss read every step): so that the
-    driver's own run carries them.  The headline keys of the JSON line are untouched."""
+    process right after the headline, the same way (captured step, 10 warm-up + 20 timed steps, loss read every step): so that a
+    --full run carries them.  The headline keys of the JSON line are untouched."""
     out = {}
     for model, dataset in (("DeepSense", "MOD"), ("SW_Transformer", "HAR4")):
         if (model, dataset) == (a.model, a.dataset):
@@ -870,6 +885,58 @@ def secondary_workloads(a, device):
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
     return out
+
+
+class InitialState:
+    """--dump-outputs: the training state before the first step, and putting it back.  Repeated steps cannot reproduce each other: the
+    float atomics of the backward kernels sum in a run-dependent order, and AdamW turns those last-bit differences into different weights
+    within a few steps (two runs of 3 steps: gradients 1e-2 apart).  One step from the same state differs by that rounding only (loss 2e-7,
+    gradients 1e-4 apart, whatever number of steps ran before).  Restored:
+    every parameter and buffer (the arena's fp32 masters, then their bf16 shadow), both AdamW moments, the optimizer's step counter and
+    the device RNG words of dropout and of the view draws; all in place, at the addresses the captured graphs hold."""
+
+    def __init__(self, step):
+        self.state = {k: v.detach().clone() for k, v in step.model.state_dict().items()}
+
+    @torch.no_grad()
+    def restore(self, step, device, rank):
+        from focal_amd import ops, runtime
+        torch.cuda.synchronize()
+        cur = step.model.state_dict()
+        for k, v in self.state.items():
+            cur[k].copy_(v)
+        for ar in step.opt._arenas():
+            for t in ar.moments():
+                t.zero_()
+            ar.sync_shadow(force=True)
+        if step.opt._step_state is not None:
+            step.opt._step_state.zero_()
+        runtime.rng_state(device).copy_(ops.new_rng_state(DROPOUT_SEED + rank, device))
+        runtime.view_state(device).copy_(ops.new_rng_state(VIEW_SEED, device))
+        np.random.seed(VIEW_SEED)
+        torch.cuda.synchronize()
+
+
+def dump_outputs(step, out_dir):
+    """--dump-outputs: what the timed step hands its caller -- the loss, its terms and the gradients it left in the arena -- as .npy
+    files.  Gradients are flattened in named_parameters order (frozen parameters contribute zeros) and cut to a fixed sample of
+    DUMP_MAX_ELEMS elements (seed 0, in index order), the same sample for every build of the same model.  The updated weights are not
+    written: AdamW's first step from zero moments moves every weight by +-lr after the SIGN of its gradient, so the weights whose
+    gradient is rounding noise (~750 of 11.8 M) land 2 lr apart from run to run; the gradients carry the same information continuously."""
+    torch.cuda.synchronize()
+    params = [p for _, p in step.model.named_parameters()]
+    flat_g = torch.cat([p.grad.detach().reshape(-1).float() if p.grad is not None else torch.zeros(p.numel(), device=p.device) for p in params])
+    arrays = {"loss": step.loss.detach().double().reshape(1)}
+    terms = getattr(step.loss_fn, "last_terms", None)
+    if terms is not None:
+        arrays["loss_terms"] = terms.detach().double().reshape(-1)
+    if flat_g.numel() > DUMP_MAX_ELEMS:
+        idx = torch.randperm(flat_g.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+        flat_g = flat_g[idx.to(flat_g.device)]
+    arrays["gradients"] = flat_g
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), v.cpu().numpy())
 
 
 def main():
@@ -904,7 +971,12 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import ablate_shim
         ablate_shim.install()
+    from focal_amd import runtime
+    runtime.rng_state(device, seed=DROPOUT_SEED + rank)  # per rank, as the library's own draw is
+    runtime.view_state(device, seed=VIEW_SEED)           # one word for the whole job, as the library's broadcast makes it
+    np.random.seed(VIEW_SEED)                            # --views random-host: the augmenter's host draws
     step = Step(a, device)
+    initial = InitialState(step) if a.dump_outputs else None
     if a.roofline_only:
         print(json.dumps(roofline(a, step, device)))
         return
@@ -918,14 +990,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     last_loss = step.loss.item()
+    if a.dump_outputs:  # every rank: the step holds collectives
+        initial.restore(step, device, rank)
+        with torch.cuda.stream(side):
+            step.last_run()
+            step.loss.item()
+        if rank == 0:
+            dump_outputs(step, a.dump_outputs)
+    # everything below the headline runs with --full only
     with torch.cuda.stream(side):
-        dp = dp_diagnostics(a, step, world, device, graphed) if world > 1 else None
+        dp = dp_diagnostics(a, step, world, device, graphed) if (a.full and world > 1) else None
     with torch.cuda.stream(side):  # the stream the warm-up and the timed steps ran on: its allocator pools are the warm ones
-        rl = roofline(a, step, device, dt / a.steps * 1e3) if (rank == 0 and not a.no_roofline) else None
-    # (the plain single-GPU run only: profiling / diagnostic invocations -- --no-graph, --no-roofline, --no-cpu-baseline -- measure one workload)
+        rl = roofline(a, step, device, dt / a.steps * 1e3) if (a.full and rank == 0 and not a.no_roofline) else None
+    # (--full on the default single-GPU configuration only: profiling / diagnostic invocations -- --no-graph, --no-roofline, --no-cpu-baseline -- measure one workload)
     plain = not (a.no_secondary or a.no_graph or a.no_roofline or a.no_cpu_baseline or a.no_dropout or a.from_host or a.views != "fixed" or a.batch != 256)
-    sec = secondary_workloads(a, device) if (rank == 0 and world == 1 and plain and a.model == "SW_Transformer" and a.dataset == "MOD") else None
-    cb = cpu_baseline(a, step.cfg) if (rank == 0 and world == 1 and not a.no_cpu_baseline) else None
+    sec = secondary_workloads(a, device) if (a.full and rank == 0 and world == 1 and plain and a.model == "SW_Transformer" and a.dataset == "MOD") else None
+    cb = cpu_baseline(a, step.cfg) if (a.full and rank == 0 and world == 1 and not a.no_cpu_baseline) else None
     if world > 1:
         dist.barrier()  # the other ranks wait here while rank 0 measures its roofline: all leave the process group together
     if rank == 0:

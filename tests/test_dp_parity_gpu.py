@@ -34,7 +34,7 @@ def test_bench_contract_with_two_ranks(model):
                FOCAL_LOSS_SHARD="1" if model == "SW_Transformer" else "0")  # both segmentations of the step (sharded / replicated head)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541" if model == "DeepSense" else "29542", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4",
-           "--warmup", "2", "--batch", "16", "--model", model]  # no diagnostic flags: rank 0 also measures its roofline (local steps)
+           "--warmup", "2", "--batch", "16", "--model", model, "--full"]  # --full: rank 0 also measures its roofline (local steps), every rank the dp pieces
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     tail = (r.stdout + r.stderr)[-3000:]
     assert r.returncode == 0, tail
@@ -65,7 +65,7 @@ def test_bench_launches_its_own_ranks():
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(OMP_NUM_THREADS="8", FOCAL_BENCH_TEST_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "16", "--no-roofline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "16", "--no-roofline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     tail = (r.stdout + r.stderr)[-3000:]
     assert r.returncode == 0, tail
