@@ -183,6 +183,11 @@ PROTOTYPES = {
     "focal_window_attn_qkv_bwd": (C.c_int, [C.POINTER(AttnDesc), P, P, P, P, P, P, P, P, P]),
     "focal_fusion_attn_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, C.c_uint32, C.c_float, P]),
     "focal_fusion_attn_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P, P]),
+    "focal_loc_attn_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, C.c_uint32, C.c_float, P]),
+    "focal_loc_attn_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P]),
+    "focal_loc_stack": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P]),
+    "focal_loc_unstack_add": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P]),
+    "focal_loc_mean_bwd_add": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P]),
     "focal_cross_entropy": (C.c_int, [C.c_int, C.c_int, P, P, P, P, P]),
     "focal_small_linear_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P]),
     "focal_small_linear_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),

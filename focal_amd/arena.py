@@ -18,6 +18,16 @@ from . import ops
 ALIGN = 8  # elements: keeps every segment 32-byte (fp32) / 16-byte (bf16) aligned for vector loads
 
 
+def layout(module, is_hot):
+    """The arena's layout, host-side: ({name: (offset, numel, shape)} of the hot parameters in module order, total elements)."""
+    index, off = {}, 0
+    for n, p in module.named_parameters():
+        if is_hot(n):
+            index[n] = (off, p.numel(), tuple(p.shape))
+            off += (p.numel() + ALIGN - 1) // ALIGN * ALIGN
+    return index, off
+
+
 class ParamArena:
     def __init__(self, module, is_hot, compute_dtype):
         named = [(n, p) for n, p in module.named_parameters()]
@@ -29,11 +39,7 @@ class ParamArena:
             raise ops._lib.FocalHipError("the FOCAL HIP path needs the model on a ROCm device (no CPU fallback)")
         self.device = dev
         self.compute_dtype = compute_dtype
-        self.index = {}
-        off = 0
-        for n, p in hot:
-            self.index[n] = (off, p.numel(), tuple(p.shape))
-            off += (p.numel() + ALIGN - 1) // ALIGN * ALIGN
+        self.index, off = layout(module, is_hot)
         self.size = off
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(off, dtype=torch.float32, device=dev)

@@ -5,15 +5,18 @@ import torch.nn as nn
 from . import runtime
 from .arena import ParamArena
 
+# (loc_context_layers. / loc_fusion_layer. -- SW_Transformer's location fusion -- exist only on multi-location datasets and are hot there:
+# focal_amd/loc_engine.py.  DeepSense's loc_fusion_layers. (MeanFusionBlock, no parameters on the shipped configs) stays dead.)
 DEAD_PREFIXES = ("patch_embed.", "class_layer.", "mod_fusion_layers.", "absolute_pos_embed.", "mod_extractors.",
-                 "loc_fusion_layers.", "loc_context_layers.", "loc_fusion_layer.")
+                 "loc_fusion_layers.")
 
 
 HEAD_PREFIXES = ("class_layer.", "mod_fusion_layers.")
 
 
 def is_hot(name):
-    """Parameters that receive a gradient in FOCAL pretraining."""
+    """Parameters that receive a gradient in FOCAL pretraining; on a multi-location dataset that includes the
+    location fusion of SW_Transformer (on single-location datasets those parameters do not exist: the set is unchanged)."""
     return not name.startswith(DEAD_PREFIXES)
 
 

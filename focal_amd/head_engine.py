@@ -8,31 +8,76 @@ Everything here is fp32 (activations of a few hundred KB); the products run on t
 import torch
 
 from . import ops
-from ._lib import ACT_NONE, EPI_GELU, EPI_NONE
+from ._lib import ACT_NONE, EPI_GELU
+
+
+class FusionBlock:
+    """TransformerFusionBlock (models/FusionModules.py:61-140) on the HIP kernels, forward and backward: LayerNorm over the M tokens of a
+    sample, query = the mean of the normalised tokens, nn.MultiheadAttention (head_dim 64) of that one query over them, out_proj.
+    Shared by the classifier head (M modality tokens; `compute` operands) and the location fusion of a multi-location dataset
+    (focal_amd/loc_engine.py: M = L location tokens; fp32 operands).  x [B*M, E] fp32 -> y [B, E] fp32."""
+
+    def __init__(self, backbone, prefix, heads, fp32_operands=False):
+        self.bb, self.pre, self.heads, self.fp32_operands = backbone, prefix, heads, fp32_operands
+
+    def _code(self):
+        return ops.code(torch.float32 if self.fp32_operands else self.bb.compute_dtype)
+
+    def _w(self, ar, name):
+        return ar.master(name) if self.fp32_operands else ar.operand(name)
+
+    def _lin(self, x, w, b):
+        f32 = ops.code(torch.float32)
+        d = ops.linear_desc(self._code(), x.shape[0], w.shape[0], x.shape[1], f32, f32)
+        y = torch.empty(x.shape[0], w.shape[0], dtype=torch.float32, device=x.device)
+        ops.linear_fwd(d, x, w, b, None, y)
+        return y, d
+
+    @staticmethod
+    def _lin_bwd(d, dy, x, w, gw, gb):
+        ops.linear_bwd_weight(d, dy, x, gw, gb)
+        dx = torch.empty_like(x)
+        ops.linear_bwd_data(d, dy, w, None, dx)
+        return dx
+
+    def forward(self, x, B, M, p_attn, rng, stream_id):
+        ar, pre, E = self.bb.arena(), self.pre, x.shape[1]
+        xn, st = ops.layernorm_fwd(x, ar.master(f"{pre}.norm1.weight"), ar.master(f"{pre}.norm1.bias"), torch.float32)
+        qin = ops.mean_time(xn, B, M, E)
+        # nn.MultiheadAttention packs W_q | W_k | W_v as in_proj_weight [3E, E]: row slices of the arena, no copies
+        w_in, b_in = self._w(ar, f"{pre}.mha.in_proj_weight"), ar.master(f"{pre}.mha.in_proj_bias")
+        q, d_q = self._lin(qin, w_in[:E], b_in[:E])
+        kv, d_kv = self._lin(xn, w_in[E:], b_in[E:])
+        o = torch.empty(B, E, dtype=torch.float32, device=x.device)
+        probs = torch.empty(B, self.heads, M, dtype=torch.float32, device=x.device)
+        weights = torch.empty_like(probs)
+        ops.fusion_attn_fwd(B, M, E, self.heads, q, kv, o, probs, weights, rng, stream_id, p_attn)
+        y, d_out = self._lin(o, self._w(ar, f"{pre}.mha.out_proj.weight"), ar.master(f"{pre}.mha.out_proj.bias"))
+        return y, dict(x=x, st=st, xn=xn, qin=qin, q=q, d_q=d_q, kv=kv, d_kv=d_kv, o=o, probs=probs, weights=weights, d_out=d_out,
+                       B=B, M=M, E=E)
+
+    def backward(self, sv, dy):
+        """dy [B, E] fp32 -> dx [B*M, E]; the block's parameter gradients accumulate into the arena."""
+        ar, pre, B, M, E = self.bb.arena(), self.pre, sv["B"], sv["M"], sv["E"]
+        do = self._lin_bwd(sv["d_out"], dy, sv["o"], self._w(ar, f"{pre}.mha.out_proj.weight"), ar.g(f"{pre}.mha.out_proj.weight"),
+                           ar.g(f"{pre}.mha.out_proj.bias"))
+        dq = torch.empty(B, E, dtype=torch.float32, device=dy.device)
+        dkv = torch.empty(B * M, 2 * E, dtype=torch.float32, device=dy.device)
+        ops.fusion_attn_bwd(B, M, E, self.heads, sv["q"], sv["kv"], sv["probs"], sv["weights"], do, dq, dkv)
+        w_in, gw, gb = self._w(ar, f"{pre}.mha.in_proj_weight"), ar.g(f"{pre}.mha.in_proj_weight"), ar.g(f"{pre}.mha.in_proj_bias")
+        dqin = self._lin_bwd(sv["d_q"], dq, sv["qin"], w_in[:E], gw[:E], gb[:E])
+        dxn = self._lin_bwd(sv["d_kv"], dkv, sv["xn"], w_in[E:], gw[E:], gb[E:])
+        ops.loc_mean_bwd_add(dqin, dxn.view(B, M, E))  # the query is the mean of the M normalised tokens: dxn += dqin / M
+        dx = torch.empty_like(sv["x"])
+        ops.layernorm_bwd(dxn, sv["x"], sv["st"], ar.master(f"{pre}.norm1.weight"), dx, False, ar.g(f"{pre}.norm1.weight"),
+                          ar.g(f"{pre}.norm1.bias"))
+        return dx
 
 
 class ClassifierHead:
     def __init__(self, backbone, fusion_prefix=None, heads=0, p_attn=0.0):
         self.bb, self.fusion, self.heads, self.p_attn = backbone, fusion_prefix, heads, p_attn
-
-    # ------------------------------------------------------------------------------------------------ helpers
-    def _lin(self, x, w, b, act_in=ACT_NONE, epi=EPI_NONE, act_grad=None):
-        ar, cc, f32 = self.bb.arena(), ops.code(self.bb.compute_dtype), ops.code(torch.float32)
-        M, K = x.shape
-        N = ar.index[w][2][0]
-        d = ops.linear_desc(cc, M, N, K, f32, f32, act_in, epi)
-        y = torch.empty(M, N, dtype=torch.float32, device=x.device)
-        ops.linear_fwd(d, x, ar.operand(w), ar.master(b), None, y, act_grad)
-        return y, d
-
-    def _lin_bwd(self, d, dy, x, w, b, need_dx=True, aux=None):
-        ar = self.bb.arena()
-        ops.linear_bwd_weight(d, dy, x, ar.g(w), ar.g(b))
-        if not need_dx:
-            return None
-        dx = torch.empty_like(x)
-        ops.linear_bwd_data(d, dy, ar.operand(w), aux, dx)
-        return dx
+        self.block = FusionBlock(backbone, fusion_prefix, heads) if fusion_prefix is not None else None
 
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, feats, training):
@@ -41,23 +86,9 @@ class ClassifierHead:
         sv = {"training": training}
         if self.fusion is not None:
             B, M, E = feats.shape
-            pre = self.fusion
-            x = feats.reshape(B * M, E).contiguous()
-            xn, st = ops.layernorm_fwd(x, ar.master(f"{pre}.norm1.weight"), ar.master(f"{pre}.norm1.bias"), torch.float32)
-            qin = ops.mean_time(xn, B, M, E)
-            # nn.MultiheadAttention packs W_q | W_k | W_v as in_proj_weight [3E, E]: views of the arena, no copies
-            wq, wkv = _ProjView(ar, f"{pre}.mha.in_proj_weight", 0, E), _ProjView(ar, f"{pre}.mha.in_proj_weight", E, 3 * E)
-            bq, bkv = _ProjView(ar, f"{pre}.mha.in_proj_bias", 0, E), _ProjView(ar, f"{pre}.mha.in_proj_bias", E, 3 * E)
-            q = self._proj(qin, wq, bq)
-            kv = self._proj(xn, wkv, bkv)
-            o = torch.empty(B, E, dtype=torch.float32, device=x.device)
-            probs = torch.empty(B, self.heads, M, dtype=torch.float32, device=x.device)
-            weights = torch.empty_like(probs)
             p = self.p_attn if training else 0.0
-            ops.fusion_attn_fwd(B, M, E, self.heads, q, kv, o, probs, weights, bb.rng_state() if p > 0 else None, 0x7F00, p)
-            y, d_out = self._lin(o, f"{pre}.mha.out_proj.weight", f"{pre}.mha.out_proj.bias")
-            sv.update(x=x, st=st, xn=xn, qin=qin, q=q, kv=kv, o=o, probs=probs, weights=weights, d_out=d_out, B=B, M=M, E=E)
-            h = y
+            h, fs = self.block.forward(feats.reshape(B * M, E).contiguous(), B, M, p, bb.rng_state() if p > 0 else None, 0x7F00)
+            sv["fusion"] = fs
         else:
             h = feats.contiguous()
         sv["h_in"] = h
@@ -75,13 +106,6 @@ class ClassifierHead:
             return logits, sv
         logits = ops.small_linear_fwd(h, ar.master("class_layer.0.weight"), ar.master("class_layer.0.bias"))
         return logits, sv
-
-    def _proj(self, x, w, b):
-        cc, f32 = ops.code(self.bb.compute_dtype), ops.code(torch.float32)
-        d = ops.linear_desc(cc, x.shape[0], w.rows, x.shape[1], f32, f32)
-        y = torch.empty(x.shape[0], w.rows, dtype=torch.float32, device=x.device)
-        ops.linear_fwd(d, x, w.operand(), b.master(), None, y)
-        return y
 
     # ------------------------------------------------------------------------------------------------ backward
     def backward(self, sv, dlogits):
@@ -105,41 +129,6 @@ class ClassifierHead:
                                       ar.g("class_layer.0.bias"), need_dx)
         if self.fusion is None:
             return dh if train_encoders else None  # finetuning: the encoders in front are frozen
-        pre, B, M, E = self.fusion, sv["B"], sv["M"], sv["E"]
-        do = self._lin_bwd(sv["d_out"], dh, sv["o"], f"{pre}.mha.out_proj.weight", f"{pre}.mha.out_proj.bias")
-        dq = torch.empty(B, E, dtype=torch.float32, device=do.device)
-        dkv = torch.empty(B * M, 2 * E, dtype=torch.float32, device=do.device)
-        ops.fusion_attn_bwd(B, M, E, self.heads, sv["q"], sv["kv"], sv["probs"], sv["weights"], do, dq, dkv)
-        wq, wkv = _ProjView(ar, f"{pre}.mha.in_proj_weight", 0, E), _ProjView(ar, f"{pre}.mha.in_proj_weight", E, 3 * E)
-        bq, bkv = _ProjView(ar, f"{pre}.mha.in_proj_bias", 0, E), _ProjView(ar, f"{pre}.mha.in_proj_bias", E, 3 * E)
-        dqin = self._proj_bwd(dq, sv["qin"], wq, bq)
-        dxn = self._proj_bwd(dkv, sv["xn"], wkv, bkv)
-        dxn.view(B, M, E).add_(dqin.view(B, 1, E) / M)  # the query is the mean of the M normalised tokens
-        dx = torch.empty_like(sv["x"])                  # gradient w.r.t. the features (propagated further in supervised training only)
-        ops.layernorm_bwd(dxn, sv["x"], sv["st"], ar.master(f"{pre}.norm1.weight"), dx, False,
-                          ar.g(f"{pre}.norm1.weight"), ar.g(f"{pre}.norm1.bias"))
-        return dx.view(B, M, E) if train_encoders else None
-
-    def _proj_bwd(self, dy, x, w, b):
-        cc, f32 = ops.code(self.bb.compute_dtype), ops.code(torch.float32)
-        d = ops.linear_desc(cc, x.shape[0], w.rows, x.shape[1], f32, f32)
-        ops.linear_bwd_weight(d, dy, x, w.grad(), b.grad())
-        dx = torch.empty_like(x)
-        ops.linear_bwd_data(d, dy, w.operand(), None, dx)
-        return dx
-
-
-class _ProjView:
-    """Rows [lo, hi) of a packed projection parameter (nn.MultiheadAttention's in_proj_weight / in_proj_bias) as GEMM operands."""
-
-    def __init__(self, arena, name, lo, hi):
-        self.ar, self.name, self.lo, self.hi, self.rows = arena, name, lo, hi, hi - lo
-
-    def operand(self):
-        return self.ar.operand(self.name)[self.lo:self.hi]
-
-    def master(self):
-        return self.ar.master(self.name)[self.lo:self.hi]
-
-    def grad(self):
-        return self.ar.g(self.name)[self.lo:self.hi]
+        fs = sv["fusion"]
+        dx = self.block.backward(fs, dh)  # gradient w.r.t. the features (propagated further in supervised training only)
+        return dx.view(fs["B"], fs["M"], fs["E"]) if train_encoders else None

@@ -985,6 +985,39 @@ def fusion_attn_bwd(B, M, E, heads, q, kv, probs, weights, dout, dq, dkv):
     check(_lib.load().focal_fusion_attn_bwd(B, M, E, heads, _p(q), _p(kv), _p(probs), _p(weights), _p(dout), _p(dq), _p(dkv), _stream()))
 
 
+def loc_attn_fwd(N, L, E, heads, qkv, out, probs, weights, rng, stream_id, p_drop):
+    _need_cuda(qkv, out, probs, weights)
+    check(_lib.load().focal_loc_attn_fwd(N, L, E, heads, _p(qkv), _p(out), _p(probs), _p(weights), _p(rng), stream_id, p_drop, _stream()))
+
+
+def loc_attn_bwd(N, L, E, heads, qkv, probs, weights, dout, dqkv):
+    _need_cuda(qkv, probs, weights, dout, dqkv)
+    check(_lib.load().focal_loc_attn_bwd(N, L, E, heads, _p(qkv), _p(probs), _p(weights), _p(dout), _p(dqkv), _stream()))
+
+
+def loc_stack(feats, out):
+    """out [N, L, E] <- the L location features [N, E] (one launch)."""
+    _need_cuda(out, *feats)
+    N, L, E = out.shape
+    ptrs = (C.c_void_p * L)(*[f.data_ptr() for f in feats])
+    check(_lib.load().focal_loc_stack(N, L, E, ptrs, _p(out), _stream()))
+
+
+def loc_unstack_add(a, b, dst):
+    """dst[l] [N, E] <- a[:, l] + b[:, l] for a, b [N, L, E]."""
+    _need_cuda(a, b, *dst)
+    N, L, E = a.shape
+    ptrs = (C.c_void_p * L)(*[d.data_ptr() for d in dst])
+    check(_lib.load().focal_loc_unstack_add(N, L, E, _p(a), _p(b), ptrs, _stream()))
+
+
+def loc_mean_bwd_add(dq, dx):
+    """dx [N, L, E] += dq [N, E] / L (the gradient of a mean over the L tokens)."""
+    _need_cuda(dq, dx)
+    N, L, E = dx.shape
+    check(_lib.load().focal_loc_mean_bwd_add(N, L, E, _p(dq), _p(dx), _stream()))
+
+
 def small_linear_fwd(x, w, bias):
     B, K = x.shape
     y = torch.empty(B, w.shape[0], dtype=torch.float32, device=x.device)

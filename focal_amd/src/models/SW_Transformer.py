@@ -4,7 +4,9 @@ reference (models/SW_Transformer.py), executed on the MI355X HIP kernels.
 `forward(freq_x, class_head=False, proj_head=...)` is the FOCAL pretraining path (reference :210-268, :294-304).
 The classifier path (`class_head=True`: TransformerFusionBlock over the modality tokens + class layer, reference :244-276) runs for
 the finetune stage (frozen encoders, head trained) and for supervised training from scratch (gradient flows on into the encoders and
-the patch embedding); multi-location fusion raises.
+the patch embedding).  On a multi-location dataset the FOCAL pretraining path runs the reference's location fusion (:126-150,
+:226-242: per modality, loc_context_layers + loc_fusion_layer over the L location features) as one HIP stage per modality
+(focal_amd/loc_engine.py); the classifier path on such a dataset raises.
 """
 import os
 import sys
@@ -19,9 +21,10 @@ if _ROOT not in sys.path:
 from focal_amd import runtime  # noqa: E402
 from focal_amd.backbone import HipBackbone, run_stage  # noqa: E402
 from focal_amd.head_engine import ClassifierHead  # noqa: E402
+from focal_amd.loc_engine import LocFusionStage, run_loc_stage  # noqa: E402
 from focal_amd.swin_engine import ProjectorHead, SwinModEncoder  # noqa: E402
 from input_utils.padding_utils import get_padded_size  # noqa: E402
-from models.FusionModules import TransformerFusionBlock  # noqa: E402
+from models.FusionModules import LocContextLayer, TransformerFusionBlock  # noqa: E402
 from models.SwinModules import BasicLayer, PatchEmbed, PatchMerging  # noqa: E402
 
 
@@ -46,8 +49,13 @@ class SW_Transformer(HipBackbone):
 
     def init_encoder(self) -> None:
         cfg, dcfg = self.config, self.args.dataset_config
-        if len(self.locations) != 1:
-            raise NotImplementedError("the MI355X hot path covers single-location datasets (MOD); see DESIGN.md")
+        if len(self.locations) * len(self.modalities) > 8:
+            # the encoder index is a 3-bit field of every Swin dropout stream id (swin_engine: ((view * 8 + index) * 64 + block) * 8 + site):
+            # a ninth encoder would draw the masks of the next view's first encoder
+            raise NotImplementedError(f"at most 8 (location, modality) encoders (got {len(self.locations)} x {len(self.modalities)})")
+        if len(self.locations) > 1 and (self.supervised or getattr(self.args, "stage", "pretrain") == "finetune"):
+            raise NotImplementedError("class_head=True on a multi-location dataset needs location fusion in the classifier head "
+                                      "(focal_amd/head_engine.py); only FOCAL pretraining runs it (focal_amd/loc_engine.py)")
         self.freq_interval_layers = nn.ModuleDict()
         self.patch_embed = nn.ModuleDict()
         self.absolute_pos_embed = nn.ModuleDict()
@@ -95,6 +103,16 @@ class SW_Transformer(HipBackbone):
                                                heads=cfg["time_freq_head_num"], pad_img=padded)
                 if spectrum // patch[1] > grid[1] or self.num_segments > grid[0]:
                     raise ValueError("padded patch grid smaller than the input")
+        if len(self.locations) > 1:
+            # location fusion, as the reference builds it: per modality loc_block_num encoder layers + one attention fusion block
+            self.loc_context_layers = nn.ModuleDict()
+            self.loc_fusion_layer = nn.ModuleDict()
+            E = cfg["loc_out_channels"]
+            for mod in self.modalities:
+                self.loc_context_layers[mod] = nn.Sequential(*[
+                    LocContextLayer(d_model=E, nhead=cfg["loc_head_num"], dim_feedforward=E, dropout=cfg["dropout_ratio"], batch_first=True)
+                    for _ in range(cfg["loc_block_num"])])
+                self.loc_fusion_layer[mod] = TransformerFusionBlock(E, cfg["loc_head_num"], cfg["dropout_ratio"], cfg["dropout_ratio"])
         out_dim = dcfg["FOCAL"]["emb_dim"]
         self.mod_projectors = nn.ModuleDict()
         for mod in self.modalities:
@@ -108,8 +126,12 @@ class SW_Transformer(HipBackbone):
             self.class_layer = nn.Sequential(nn.Linear(self.sample_dim, n_cls))
         else:
             self.class_layer = nn.Sequential(nn.Linear(self.sample_dim, cfg["fc_dim"]), nn.GELU(), nn.Linear(cfg["fc_dim"], n_cls))
-        self._encoders = {(loc, mod): SwinModEncoder(self, loc, mod, mi)
-                          for loc in self.locations for mi, mod in enumerate(self.modalities)}
+        # (the encoder index keys the dropout streams: location-major, so a single-location dataset keeps index = modality index)
+        M = len(self.modalities)
+        self._encoders = {(loc, mod): SwinModEncoder(self, loc, mod, li * M + mi)
+                          for li, loc in enumerate(self.locations) for mi, mod in enumerate(self.modalities)}
+        self._loc_stages = ({mod: LocFusionStage(self, mod, mi) for mi, mod in enumerate(self.modalities)}
+                            if len(self.locations) > 1 else {})
         self._heads = {mod: ProjectorHead(self, mod) for mod in self.modalities}
         self._class_head = ClassifierHead(self, "mod_fusion_layers", cfg["loc_head_num"], cfg["dropout_ratio"])
 
@@ -138,7 +160,9 @@ class SW_Transformer(HipBackbone):
         order = list(range(len(self.modalities)))
         tokens = [self.geometry[loc][m]["stages"][0]["H"] * self.geometry[loc][m]["stages"][0]["W"] for m in self.modalities]
         order.sort(key=lambda i: -tokens[i])  # (stable: equal modalities keep the configuration order)
-        for mi in order:
+        if self._loc_stages:
+            self._forward_locations(freq_x, proj_head, view, dev, cur, point, order, out)
+        for mi in (order if not self._loc_stages else ()):
             mod = self.modalities[mi]
             # stream per modality; with one backbone pass per view the two passes of a step alternate between two sets of streams so
             # that they overlap.  One pass per step (views_share_pass) always uses the same set -- the first modality stays on the
@@ -153,6 +177,24 @@ class SW_Transformer(HipBackbone):
         if not defer_join:  # FOCAL.forward joins once after both views so that their encoders overlap
             runtime.join_all(dev)
         return {mod: out[mod] for mod in self.modalities}
+
+    def _forward_locations(self, freq_x, proj_head, view, dev, cur, point, order, out):
+        """Multi-location dataset: the L*M encoders fork from one point, each on its own stream; a modality's location fusion waits for
+        its own L encoders and runs, with the projector after it, on the caller's stream.  (Not on one of the encoders' side streams:
+        a side stream joined into another side stream inside a captured step makes hipStreamEndCapture fault -- forked streams join the
+        capture's origin only, docs/DESIGN_rounds_1_4.md.  The fusion stages of the M modalities are a few dozen small launches each.)"""
+        M = len(self.modalities)
+        for mi in order:
+            mod = self.modalities[mi]
+            feats = []
+            for li, loc in enumerate(self.locations):
+                st = runtime.fork_from(dev, li * M + mi, point)
+                with torch.cuda.stream(st):
+                    feats.append(run_stage(self, self._encoders[(loc, mod)], freq_x[loc][mod], view, self.training))
+                if st != cur:
+                    cur.wait_stream(st)  # (an event on st now: that stream carries this one encoder)
+            f = run_loc_stage(self._loc_stages[mod], feats, view, self.training)
+            out[mod] = run_stage(self, self._heads[mod], f) if proj_head else f
 
     def forward_classifier(self, freq_x):
         """`backbone(freq_x, class_head=True)` -> logits (reference: models/SW_Transformer.py:269-276).  This is the finetuning path: the encoders in front run

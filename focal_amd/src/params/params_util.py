@@ -9,7 +9,7 @@ from input_utils.yaml_utils import load_yaml
 _FRAMEWORK_MODE = {"FOCAL": "contrastive", "no": "supervised"}
 _DEFAULT_TASK = {"ACIDS": "vehicle_classification", "MOD": "vehicle_classification",
                  "RealWorld_HAR": "activity_classification", "PAMAP2": "activity_classification",
-                 "HAR4": "activity_classification"}
+                 "HAR4": "activity_classification", "HAR3LOC": "activity_classification"}
 
 
 def parse_device_list(device=""):

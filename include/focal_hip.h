@@ -527,6 +527,23 @@ int focal_fusion_attn_fwd(int B, int M, int E, int heads, const float* q, const 
 int focal_fusion_attn_bwd(int B, int M, int E, int heads, const float* q, const float* kv, const float* probs, const float* weights,
                           const float* dout, float* dq, float* dkv, void* stream);
 int focal_cross_entropy(int B, int C, const float* logits, const long* labels, float* loss, float* dlogits, void* stream);
+
+/* ------------------------------------------------------------------------------------------------ location fusion (SW_Transformer)
+ * Multi-location datasets: per modality, the L location features of a sample are a sequence of L tokens that runs through
+ * loc_block_num nn.TransformerEncoderLayer and one TransformerFusionBlock (models/SW_Transformer.py, focal_amd/loc_engine.py).
+ * focal_loc_attn_*: the encoder layer's self-attention core, nn.MultiheadAttention semantics with head_dim 64: qkv [N*L, 3E] rows
+ * (n, i) = {q | k | v} (in_proj applied), out [N*L, E] (before out_proj); probs / weights [N, heads, L, L] = softmax(q k^T / 8) and
+ * softmax x attention-dropout mask (saved for backward).  Backward writes dqkv [N*L, 3E] in the same packing.  2 <= L <= 8,
+ * E = heads * 64 <= 256.  One workgroup per sequence.
+ * focal_loc_stack: out [N, L, E] <- feats[l] [N, E] (L device pointers, host array).  focal_loc_unstack_add: dst[l] [N, E] <-
+ * a[:, l, :] + b[:, l, :].  focal_loc_mean_bwd_add: dx [N, L, E] += dq [N, E] / L.  E % 4 == 0, 16-byte aligned tensors. */
+int focal_loc_attn_fwd(int N, int L, int E, int heads, const float* qkv, float* out, float* probs, float* weights, const uint32_t* rng,
+                       uint32_t stream_id, float p_drop, void* stream);
+int focal_loc_attn_bwd(int N, int L, int E, int heads, const float* qkv, const float* probs, const float* weights, const float* dout,
+                       float* dqkv, void* stream);
+int focal_loc_stack(int N, int L, int E, const float* const* feats, float* out, void* stream);
+int focal_loc_unstack_add(int N, int L, int E, const float* a, const float* b, float* const* dst, void* stream);
+int focal_loc_mean_bwd_add(int N, int L, int E, const float* dq, float* dx, void* stream);
 /* The class layer nn.Linear(K -> n_cls) (a few output columns, fp32): y = x w^T + bias; backward accumulates dw / dbias (+=) and
  * writes dx when it is non-NULL. */
 int focal_small_linear_fwd(int B, int N, int K, const float* x, const float* w, const float* bias, float* y, void* stream);

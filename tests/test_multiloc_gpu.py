@@ -1,0 +1,414 @@
+"""Location fusion of SW_Transformer (focal_amd/loc_engine.py, csrc/loc.hip) on the GPU: the attention core and the encoder layer
+against float64 restatements, the whole FOCAL step on HAR3LOC against the reference fixture (gen_golden_multiloc.py), the captured
+step, dropout, and train.py end to end."""
+import argparse
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+from conftest import no_dropout, record_observed
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+
+def _attn_ref(qkv, N, L, E, H, weights=None):
+    """float64 restatement of nn.MultiheadAttention's core over packed q | k | v rows; weights: the kernel's dropped weights."""
+    qkv = qkv.double().view(N, L, 3, H, 64)
+    q, k, v = qkv[:, :, 0].transpose(1, 2), qkv[:, :, 1].transpose(1, 2), qkv[:, :, 2].transpose(1, 2)  # [N, H, L, 64]
+    p = torch.softmax(q @ k.transpose(-1, -2) / 8.0, dim=-1)
+    w = p if weights is None else weights.double()
+    return (w @ v).transpose(1, 2).reshape(N * L, E), p
+
+
+@pytest.mark.parametrize("L", [2, 3, 8])
+@pytest.mark.parametrize("p_drop", [0.0, 0.2])
+def test_loc_attention_core_against_float64(L, p_drop):
+    from focal_amd import ops, runtime
+    N, E, H = 512, 256, 4
+    g = torch.Generator().manual_seed(10 + L)
+    qkv = (torch.randn(N * L, 3 * E, generator=g) * 1.5).cuda()
+    dout = torch.randn(N * L, E, generator=g).cuda()
+    out = torch.empty(N * L, E, device="cuda")
+    probs = torch.empty(N, H, L, L, device="cuda")
+    weights = torch.empty_like(probs)
+    rng = runtime.rng_state("cuda") if p_drop > 0 else None
+    ops.loc_attn_fwd(N, L, E, H, qkv, out, probs, weights, rng, 0x40001234, p_drop)
+    dqkv = torch.empty_like(qkv)
+    ops.loc_attn_bwd(N, L, E, H, qkv, probs, weights, dout, dqkv)
+    torch.cuda.synchronize()
+    x = qkv.cpu().double().requires_grad_(True)
+    w_rec = weights.cpu().double()
+    if p_drop > 0:  # the kernel's mask, recovered from its recorded weights: 0 or 1 / (1 - p)
+        mask = torch.where(probs.cpu().double() > 0, w_rec / probs.cpu().double(), torch.zeros_like(w_rec))
+        ok = (mask == 0) | ((mask - 1 / (1 - p_drop)).abs() < 1e-4)
+        assert bool(ok.all())
+        mask = torch.where(mask == 0, 0.0, 1 / (1 - p_drop))
+    ref_o, ref_p = _attn_ref(x, N, L, E, H)
+    if p_drop > 0:
+        ref_o, _ = _attn_ref(x, N, L, E, H, None)
+        xx = x.view(N, L, 3, H, 64)
+        q, k, v = xx[:, :, 0].transpose(1, 2), xx[:, :, 1].transpose(1, 2), xx[:, :, 2].transpose(1, 2)
+        pp = torch.softmax(q @ k.transpose(-1, -2) / 8.0, dim=-1)
+        ref_o = ((pp * mask) @ v).transpose(1, 2).reshape(N * L, E)
+    (ref_o * dout.cpu().double()).sum().backward()
+    scale_o, scale_g = ref_o.abs().max().item(), x.grad.abs().max().item()
+    e_p = (probs.cpu().double() - ref_p.detach()).abs().max().item()
+    e_o = (out.cpu().double() - ref_o.detach()).abs().max().item() / scale_o
+    e_g = (dqkv.cpu().double() - x.grad).abs().max().item() / scale_g
+    record_observed(f"loc_attn.L{L}.p{p_drop}.fwd_rel", e_o)
+    record_observed(f"loc_attn.L{L}.p{p_drop}.bwd_rel", e_g)
+    assert e_p < 1e-5 and e_o < 1e-5 and e_g < 1e-5, (e_p, e_o, e_g)
+
+
+class _LocOnly:
+    """A backbone holding one modality's location fusion only (the stage needs config / locations / arena / rng)."""
+
+    @staticmethod
+    def build(L, E, heads, blocks, p, ct):
+        from focal_amd.backbone import HipBackbone
+        from focal_amd.loc_engine import LocFusionStage
+        from models.FusionModules import LocContextLayer, TransformerFusionBlock
+
+        class Net(HipBackbone):
+            def __init__(self):
+                super().__init__()
+                self.config = dict(loc_out_channels=E, loc_head_num=heads, loc_block_num=blocks, dropout_ratio=p)
+                self.locations = [f"l{i}" for i in range(L)]
+                self._init_hip(argparse.Namespace(compute_dtype=ct, train_mode="contrastive", stage="pretrain"))
+                self.loc_context_layers = nn.ModuleDict({"m": nn.Sequential(*[
+                    LocContextLayer(d_model=E, nhead=heads, dim_feedforward=E, dropout=p, batch_first=True) for _ in range(blocks)])})
+                self.loc_fusion_layer = nn.ModuleDict({"m": TransformerFusionBlock(E, heads, p, p)})
+                self.stage = LocFusionStage(self, "m", 0)
+        return Net()
+
+
+def _torch_reference(net, feats, dy):
+    """float64 CPU: nn.TransformerEncoderLayer (the torch class itself) + TransformerFusionBlock's forward, as the reference runs them."""
+    E, heads = net.config["loc_out_channels"], net.config["loc_head_num"]
+    sd = {k: v.detach().cpu().double() for k, v in net.state_dict().items()}
+    layers = nn.Sequential(*[nn.TransformerEncoderLayer(E, heads, dim_feedforward=E, dropout=0.0, batch_first=True)
+                             for _ in range(net.config["loc_block_num"])]).double()
+    layers.load_state_dict({k[len("loc_context_layers.m."):]: v for k, v in sd.items() if k.startswith("loc_context_layers.m.")})
+    norm, mha = nn.LayerNorm(E).double(), nn.MultiheadAttention(E, heads, dropout=0.0, batch_first=True).double()
+    norm.load_state_dict({"weight": sd["loc_fusion_layer.m.norm1.weight"], "bias": sd["loc_fusion_layer.m.norm1.bias"]})
+    mha.load_state_dict({k[len("loc_fusion_layer.m.mha."):]: v for k, v in sd.items() if k.startswith("loc_fusion_layer.m.mha.")})
+    layers.train(), mha.train()
+    x = torch.stack([f.detach().cpu().double() for f in feats], dim=1).requires_grad_(True)
+    h = layers(x)
+    xn = norm(h)
+    y, _ = mha(xn.mean(dim=1, keepdim=True), xn, xn)
+    y = y.reshape(x.shape[0], E)
+    (y * dy.cpu().double()).sum().backward()
+    grads = {f"loc_context_layers.m.{k}": p.grad for k, p in layers.named_parameters()}
+    grads.update({f"loc_fusion_layer.m.norm1.{k}": p.grad for k, p in norm.named_parameters()})
+    grads.update({f"loc_fusion_layer.m.mha.{k}": p.grad for k, p in mha.named_parameters()})
+    return y.detach(), x.grad, grads
+
+
+@pytest.mark.parametrize("ct", ["fp32", "bf16"])
+@pytest.mark.parametrize("blocks", [1, 2])
+def test_loc_stage_against_torch_encoder_layer(ct, blocks):
+    """loc_block_num encoder layers + the fusion block at N = 512, L = 3: output, input gradient and every parameter gradient."""
+    from focal_amd.loc_engine import run_loc_stage
+    from oracle.weights import fill_state_dict_
+    N, L, E = 512, 3, 256
+    net = _LocOnly.build(L, E, 4, blocks, 0.0, ct)
+    fill_state_dict_(net.state_dict())
+    net = net.cuda()
+    g = torch.Generator().manual_seed(5)
+    feats = [torch.randn(N, E, generator=g).cuda().requires_grad_(True) for _ in range(L)]
+    dy = torch.randn(N, E, generator=g).cuda()
+    net.arena().zero_grad()
+    y = run_loc_stage(net.stage, feats, 0, True)
+    y.backward(dy)
+    torch.cuda.synchronize()
+    ref_y, ref_dx, ref_g = _torch_reference(net, feats, dy)
+    tol = 1e-4 if ct == "fp32" else 1e-2
+    rel = lambda a, b: (a.cpu().double() - b).abs().max().item() / max(b.abs().max().item(), 1e-12)
+    e_y = rel(y.detach(), ref_y)
+    e_dx = max(rel(f.grad, ref_dx[:, i]) for i, f in enumerate(feats))
+    record_observed(f"loc_stage.b{blocks}.{ct}.out_rel", e_y)
+    record_observed(f"loc_stage.b{blocks}.{ct}.dx_rel", e_dx)
+    assert e_y < tol and e_dx < tol, (e_y, e_dx)
+    params = dict(net.named_parameters())
+    worst = max(rel(params[k].grad, v) for k, v in ref_g.items())
+    record_observed(f"loc_stage.b{blocks}.{ct}.dparam_rel_worst", worst)
+    assert worst < tol, worst
+    assert len(ref_g) == blocks * 12 + 6
+
+
+def _har3loc(ct, dropout=False):
+    from models.SW_Transformer import SW_Transformer
+    from oracle.config import load_config
+    from oracle.weights import fill_state_dict_
+    cfg = load_config(os.path.join(ROOT, "focal_amd", "src", "data", "HAR3LOC.yaml"))
+    if not dropout:
+        cfg = no_dropout(cfg)
+    args = argparse.Namespace(model="SW_Transformer", dataset="HAR3LOC", device=torch.device("cuda"), train_mode="contrastive",
+                              learn_framework="FOCAL", stage="pretrain", task="activity_classification", tag=None,
+                              dataset_config=cfg, compute_dtype=ct)
+    net = SW_Transformer(args)
+    fill_state_dict_(net.state_dict())
+    return cfg, args, net.cuda().train()
+
+
+def _inputs(cfg):
+    from oracle.weights import synthetic_freq_input
+    dev = lambda d: {l: {m: v.cuda() for m, v in mm.items()} for l, mm in d.items()}
+    return dev(synthetic_freq_input(cfg, 8, seed=505)), dev(synthetic_freq_input(cfg, 8, seed=606))
+
+
+@pytest.mark.parametrize("ct", ["fp32", "bf16"])
+def test_har3loc_step_against_the_reference_fixture(ct):
+    from models.FOCALModules import FOCAL
+    from models.loss import FOCALLoss
+    from train_utils.optimizer import define_optimizer
+    fx = np.load(os.path.join(GOLD, "SW_Transformer_3loc_b8.npz"))
+    cfg, args, net = _har3loc(ct)
+    x1, x2 = _inputs(cfg)
+    focal, loss_fn = FOCAL(args, net), FOCALLoss(args)
+    # bf16: the embeddings reach 1.86e-2 of scale at worst (view 2, acc; 1.0-1.9e-2 over the 2 views x 2 modalities x 2 modes), above
+    # the 1e-2 of the single-location fixtures.  The excess enters with the bf16 encoder features, not in the location stage (fp32 in
+    # both modes): test_har3loc_bf16_error_enters_with_the_encoder_features.  The loss terms keep their own 1e-2 * max(1, |t|) below.
+    tol = 1e-3 if ct == "fp32" else 2e-2
+    for mode in ("eval", "train"):
+        net.train(mode == "train")
+        with torch.no_grad():
+            for v, x in (("1", x1), ("2", x2)):
+                emb, feat = net(x, class_head=False, proj_head=True), net(x, class_head=False, proj_head=False)
+                for m in cfg["modality_names"]:
+                    for name, got in (("emb", emb[m]), ("feat", feat[m])):
+                        ref = torch.from_numpy(fx[f"pass.{mode}.{name}{v}.{m}"])
+                        e = ((got.cpu() - ref).abs().max() / ref.abs().max()).item()
+                        record_observed(f"swt3loc.{mode}.{name}{v}.{m}.{ct}.max_err_over_max_ref", e)
+                        assert e < tol, (mode, name, v, m, e)
+    net.train()
+    net.arena().zero_grad()
+    f1, f2 = focal(x1, x2, proj_head=True)
+    for m in cfg["modality_names"]:
+        for v, got in (("1", f1[m]), ("2", f2[m])):
+            ref = torch.from_numpy(fx[f"train.emb{v}.{m}"])
+            e = ((got.detach().cpu() - ref).abs().max() / ref.abs().max()).item()
+            record_observed(f"swt3loc.train.emb{v}.{m}.{ct}.max_err_over_max_ref", e)
+            assert e < tol, (v, m, e)
+    loss = loss_fn(f1, f2)
+    loss.backward()
+    terms = loss_fn.last_terms.cpu().numpy()
+    for i, k in enumerate(("shared", "private", "orth", "rank", "total")):
+        ref = float(fx[f"train.loss.{k}"])
+        err = abs(terms[i] - ref) / max(1.0, abs(ref))
+        record_observed(f"swt3loc.train.loss.{k}.{ct}.abs_err_over_max1", err)
+        assert err < (1e-3 if ct == "fp32" else 1e-2), (k, terms[i], ref)
+    params = dict(net.named_parameters())
+    names = [str(n) for n in fx["train.grad_names"]]
+    assert {n for n, p in params.items() if p.grad is not None} == set(names)
+    worst, bad = 0.0, []
+    for n, ref in zip(names, fx["train.grad_norms"]):
+        got = params[n].grad.double().norm().item()
+        if n.startswith(("loc_context_layers.", "loc_fusion_layer.")):
+            assert got > 0, n
+        e = abs(got - ref) / max(ref, 1e-6)
+        worst = max(worst, e)
+        if e > (2e-3 if ct == "fp32" else 6e-2):
+            bad.append((n, got, float(ref)))
+    record_observed(f"swt3loc.train.grad_norm.{ct}.worst_rel", worst)
+    if ct == "fp32":
+        assert not bad, bad[:6]
+    else:  # every location-fusion tensor within 6e-2; of the encoders' tensors a few (stage-0 LayerNorm biases: 7-8e-2) as in test_4mod_gpu
+        assert not [b for b in bad if b[0].startswith(("loc_context_layers.", "loc_fusion_layer."))], bad[:6]
+        assert len(bad) <= max(1, len(names) * 3 // 100), bad[:6]
+    for k in (fx.files if ct == "fp32" else ()):  # (element-wise slices: fp32 only; bf16 is pinned by the norms above)
+        if k.startswith("train.gradslice."):
+            n = k[len("train.gradslice."):]
+            ref = torch.from_numpy(fx[k])
+            f = params[n].grad.detach().reshape(-1)
+            got = f[::max(1, f.numel() // 16)][:16].cpu().double()
+            e = ((got - ref).abs().max() / ref.abs().max()).item()
+            assert e < (1e-3 if ct == "fp32" else 6e-2), (n, e)
+    if ct != "fp32":
+        return
+    # three AdamW steps from the fixture's weights (fp32)
+    cfg, args, net = _har3loc(ct)
+    focal = FOCAL(args, net)
+    opt = define_optimizer(args, focal.parameters())
+    traj = []
+    for _ in range(3):
+        opt.zero_grad()
+        a, b = focal(x1, x2, proj_head=True)
+        l_ = loss_fn(a, b)
+        l_.backward()
+        opt.step()
+        traj.append(float(loss_fn.last_terms[4]))
+    ref = fx["adamw.loss_traj"]
+    e = max(abs(t - r) / max(1.0, abs(r)) for t, r in zip(traj, ref))
+    record_observed("swt3loc.adamw.loss_traj.fp32.rel", e)
+    assert e < 2e-3, (traj, ref.tolist())
+    probe = str(fx["adamw.probe_name"])
+    w = dict(net.named_parameters())[probe].detach().reshape(-1)
+    got = w[::max(1, w.numel() // 32)][:32].cpu().double()
+    assert (got - torch.from_numpy(fx["adamw.probe_after3"])).abs().max().item() < 1e-3
+
+
+def _step_state(ct, dropout, replay):
+    """loss and arena gradients of ONE optimizer step on fixed inputs, eager or through the captured step (graph_step.py)."""
+    from focal_amd import graph_step, runtime
+    from models.FOCALModules import FOCAL
+    from models.loss import FOCALLoss
+    from train_utils.optimizer import define_optimizer
+    cfg, args, net = _har3loc(ct, dropout)
+    cfg["FOCAL"]["pretrain_optimizer"]["start_lr"] = 0.0  # the weights stay put: every step sees the same model
+    x1, x2 = _inputs(cfg)
+    focal, loss_fn = FOCAL(args, net), FOCALLoss(args)
+    opt = define_optimizer(args, focal.parameters())
+    step = graph_step.CapturedTrainStep(focal, loss_fn, opt, warm_steps=1, enabled=replay)
+    out = []
+    runtime.rng_state("cuda", seed=1234)
+    for _ in range(3):
+        loss = step(x1, x2)
+        torch.cuda.synchronize()
+        out.append((float(loss), net.arena().grad.clone()))
+    return out, step
+
+
+def test_har3loc_captured_step_matches_eager():
+    eager, _ = _step_state("fp32", False, False)
+    replayed, st = _step_state("fp32", False, True)
+    assert st.replays >= 1
+    for (le, ge), (lr, gr) in zip(eager, replayed):
+        assert np.isfinite(le) and abs(le - lr) <= 1e-5 * abs(le), (le, lr)
+        e = ((ge - gr).abs().max() / ge.abs().max()).item()
+        record_observed("swt3loc.graph_vs_eager.grad_rel", e)
+        assert e <= 1e-5, e  # (not bit-identical: the split-K / weight-gradient GEMMs accumulate with fp32 atomics in any order)
+    # p = 0: two replays of the same step agree (up to the same atomics)
+    assert abs(replayed[1][0] - replayed[2][0]) <= 1e-6 * abs(replayed[1][0])
+
+
+def test_har3loc_dropout_on():
+    from focal_amd import ops, runtime
+    N, L, E, H, p = 512, 3, 256, 4, 0.2
+    qkv = torch.randn(N * L, 3 * E, device="cuda")
+    rng = runtime.rng_state("cuda")
+    ws = []
+    for sid in (0x40000001, 0x40000009):
+        out, probs = torch.empty(N * L, E, device="cuda"), torch.empty(N, H, L, L, device="cuda")
+        w = torch.empty_like(probs)
+        ops.loc_attn_fwd(N, L, E, H, qkv, out, probs, w, rng, sid, p)
+        ws.append(w)
+        n = w.numel()
+        frac = (w == 0).float().mean().item()
+        sigma = (p * (1 - p) / n) ** 0.5
+        record_observed(f"loc_attn.dropped_fraction.{sid:x}", frac)
+        assert abs(frac - p) < 4 * sigma, frac
+    assert not torch.equal(ws[0] == 0, ws[1] == 0)  # two sites, two masks
+    on, _ = _step_state("fp32", True, True)
+    assert all(np.isfinite(l_) and bool(torch.isfinite(g).all()) for l_, g in on)
+    assert on[1][0] != on[2][0] and not torch.equal(on[1][1], on[2][1])  # two replayed steps draw different masks
+
+
+def test_har3loc_bf16_error_enters_with_the_encoder_features():
+    """Where the bf16 step's deviation comes from: the location stage runs fp32 operands in both modes, so the bf16 model's
+    pre-projector features must equal the fp32 model's stage fed the bf16 encoders' features -- and the fp32 stage fed fp32 features
+    must reproduce the reference.  Then all of the bf16 excess over fp32 arrives with the encoder features."""
+    fx = np.load(os.path.join(GOLD, "SW_Transformer_3loc_b8.npz"))
+    nets = {ct: _har3loc(ct)[2].eval() for ct in ("fp32", "bf16")}
+    cfg = _har3loc("fp32")[0]
+    x1, _ = _inputs(cfg)
+    rel = lambda a, b: ((a - b).abs().max() / b.abs().max()).item()
+    with torch.no_grad():
+        for net in nets.values():
+            net.arena()
+        feats = {ct: {m: [net._encoders[(loc, m)].forward(x1[loc][m], 0, False)[0] for loc in cfg["location_names"]]
+                      for m in cfg["modality_names"]} for ct, net in nets.items()}
+        bf16_out = nets["bf16"](x1, class_head=False, proj_head=False)
+        for m in cfg["modality_names"]:
+            stage = nets["fp32"]._loc_stages[m]
+            ref = torch.from_numpy(fx[f"pass.eval.feat1.{m}"])
+            on_fp32 = stage.forward(feats["fp32"][m], 0, False)[0].cpu()
+            on_bf16 = stage.forward(feats["bf16"][m], 0, False)[0].cpu()
+            e_in = max(rel(b.cpu(), f.cpu()) for b, f in zip(feats["bf16"][m], feats["fp32"][m]))
+            e_fp32 = rel(on_fp32, ref)
+            e_same = rel(bf16_out[m].cpu(), on_bf16)
+            e_out = rel(on_bf16, ref)
+            record_observed(f"swt3loc.attribution.{m}.encoder_features_bf16_vs_fp32", e_in)
+            record_observed(f"swt3loc.attribution.{m}.stage_on_bf16_features_vs_reference", e_out)
+            assert e_fp32 < 1e-4, e_fp32    # the fp32 stage on fp32 features is the reference
+            assert e_same < 1e-5, e_same    # the bf16 model's stage output IS the fp32 stage on the bf16 features
+            assert e_out > 5 * e_fp32       # ... so the bf16 deviation is carried in by those features
+
+
+def test_loc_stage_dropout_masks_differ_between_sites_and_replays():
+    """p = 0.2 in the stage itself: every attention site of the stage (2 layers + the fusion block, 2 modalities) draws its own mask;
+    a captured forward of the stage draws fresh masks after the device seed advances and the same masks when it does not."""
+    from focal_amd import runtime
+    cfg, args, net = _har3loc("fp32", dropout=True)
+    net.arena()
+    g = torch.Generator().manual_seed(9)
+    feats = [torch.randn(512, 256, generator=g).cuda() for _ in cfg["location_names"]]
+    masks = []
+    with torch.no_grad():
+        for m in cfg["modality_names"]:
+            _, sv = net._loc_stages[m].forward(feats, 0, True)
+            for w in [ly["weights"] for ly in sv["layers"]] + [sv["fusion"]["weights"]]:
+                masks.append((w == 0).flatten()[:1536 * 3])
+                frac = (w == 0).float().mean().item()
+                assert abs(frac - 0.2) < 4 * (0.2 * 0.8 / w.numel()) ** 0.5, frac
+    for i in range(len(masks)):
+        for j in range(i + 1, len(masks)):
+            assert not torch.equal(masks[i], masks[j]), (i, j)
+    stage = net._loc_stages["acc"]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side), torch.no_grad():
+        stage.forward(feats, 0, True)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.no_grad(), torch.cuda.graph(graph):
+        y, sv = stage.forward(feats, 0, True)
+    w = sv["layers"][0]["weights"]
+    seen = []
+    for advance in (False, True, False):
+        if advance:
+            runtime.advance_step("cuda")
+        graph.replay()
+        torch.cuda.synchronize()
+        seen.append(((w == 0).clone(), y.clone()))
+    assert not torch.equal(seen[0][0], seen[1][0]) and not torch.equal(seen[0][1], seen[1][1])  # fresh masks after the seed moved
+    assert torch.equal(seen[1][0], seen[2][0]) and torch.equal(seen[1][1], seen[2][1])          # same seed, same masks, same output
+
+
+@pytest.mark.parametrize("dataset", ["MOD", "HAR4"])
+def test_single_location_arena_is_unchanged(dataset):
+    """The real ParamArena of a single-location config: index (offsets, sizes, shapes) as the single-location code laid it out."""
+    from models.SW_Transformer import SW_Transformer
+    from oracle.config import load_config
+    from test_multiloc_cpu import _single_location_layout
+    cfg = load_config(os.path.join(ROOT, "focal_amd", "src", "data", f"{dataset}.yaml"))
+    args = argparse.Namespace(model="SW_Transformer", dataset=dataset, device=torch.device("cuda"), train_mode="contrastive",
+                              learn_framework="FOCAL", stage="pretrain", task="vehicle_classification" if dataset == "MOD" else
+                              "activity_classification", tag=None, dataset_config=cfg, compute_dtype="bf16")
+    net = SW_Transformer(args).cuda()
+    ar = net.arena()
+    assert [(n, *v) for n, v in ar.index.items()] == _single_location_layout(net)
+
+
+def test_train_py_har3loc_runs_and_resumes(tmp_path):
+    src = os.path.join(ROOT, "focal_amd", "src")
+    base = [sys.executable, os.path.join(src, "train.py"), "-model=SW_Transformer", "-dataset=HAR3LOC", "-learn_framework=FOCAL",
+            "-batch_size=16", "-synthetic_batches=2"]
+    r = subprocess.run(base + ["-epochs=2"], capture_output=True, text=True, timeout=900, cwd=src)
+    log = r.stdout + r.stderr
+    assert r.returncode == 0, log[-3000:]
+    assert not re.search(r"loss[^\n]*\bnan\b", log, flags=re.I), log[-2000:]
+    wdir = os.path.join(ROOT, "weights", "HAR3LOC_SW_Transformer")
+    assert os.path.exists(os.path.join(wdir, "HAR3LOC_SW_Transformer_pretrain_latest.pt"))
+    r2 = subprocess.run(base + ["-epochs=3", "-resume"], capture_output=True, text=True, timeout=900, cwd=src)
+    assert r2.returncode == 0, (r2.stdout + r2.stderr)[-3000:]
+    assert "Total processing time" in r2.stdout + r2.stderr
