@@ -536,20 +536,29 @@ def mlp_mask_bits(d, device):
     return torch.empty(d.M, 8, dtype=torch.int32, device=device)
 
 
+def _next_ln(d, like, next_ln):
+    """The `next_ln` epilogue of the MLP forwards: the kernel's four pointers (gamma, beta, y_ln, stats) and what the wrapper returns for it,
+    (y_ln, stats) allocated here -- or four nulls and None when the caller asked for no LayerNorm."""
+    if next_ln is None:
+        return (None,) * 4, None
+    y_ln = torch.empty(d.M, d.C, dtype=like.dtype, device=like.device)
+    stats = torch.empty(d.M, 2, dtype=torch.float32, device=like.device)
+    return (_p(next_ln[0]), _p(next_ln[1]), _p(y_ln), _p(stats)), (y_ln, stats)
+
+
+def _ln_mask(ln, key):
+    """The mask pointer of the MLP backwards' fused LayerNorm backward: null without `ln`, else the mask under `key` (no dropout when absent)."""
+    return None if ln is None else C.byref(ln.get(key) or NO_DROP)
+
+
 def mlp_fwd(d, a, resid, w1, b1, w2, b2, y, next_ln=None, mask_bits=None):
     """y = resid + drop_out(drop_hidden(gelu(a w1^T + b1)) w2^T + b2) (focal_mlp_fwd); next_ln = (gamma, beta) also returns
     (LayerNorm(y) in a's dtype, stats) of the LayerNorm that reads y next.  mask_bits (ops.mlp_mask_bits) receives the hidden
     dropout's keep bits for mlp_bwd."""
     _need_cuda(a, resid, w1, b1, w2, b2, y, mask_bits)
-    if next_ln is None:
-        check(_lib.load().focal_mlp_fwd(C.byref(d), _p(a), _p(resid), _p(w1), _p(b1), _p(w2), _p(b2), _p(y), None, None, None, None,
-                                            _p(mask_bits), _stream()))
-        return None
-    y_ln = torch.empty(d.M, d.C, dtype=a.dtype, device=a.device)
-    stats = torch.empty(d.M, 2, dtype=torch.float32, device=a.device)
-    check(_lib.load().focal_mlp_fwd(C.byref(d), _p(a), _p(resid), _p(w1), _p(b1), _p(w2), _p(b2), _p(y), _p(next_ln[0]),
-                                        _p(next_ln[1]), _p(y_ln), _p(stats), _p(mask_bits), _stream()))
-    return y_ln, stats
+    ln_ptrs, out = _next_ln(d, a, next_ln)
+    check(_lib.load().focal_mlp_fwd(C.byref(d), _p(a), _p(resid), _p(w1), _p(b1), _p(w2), _p(b2), _p(y), *ln_ptrs, _p(mask_bits), _stream()))
+    return out
 
 
 def mlp_proj_supported(dtype, Cc, hidden):
@@ -564,15 +573,10 @@ def mlp_proj_fwd(d, o, x, wp, bp, drop_proj, g2, bt2, x_mid, w1, b1, w2, b2, y, 
     a2 = torch.empty(d.M, d.C, dtype=o.dtype, device=o.device)
     st2 = torch.empty(d.M, 2, dtype=torch.float32, device=o.device)
     mask = drop_proj or NO_DROP
-    if next_ln is None:
-        check(_lib.load().focal_mlp_proj_fwd(C.byref(d), _p(o), _p(x), _p(wp), _p(bp), C.byref(mask), _p(g2), _p(bt2), _p(x_mid), _p(a2), _p(st2), _p(w1), _p(b1),
-                                             _p(w2), _p(b2), _p(y), None, None, None, None, _p(mask_bits), _stream()))
-        return (a2, st2), None
-    y_ln = torch.empty(d.M, d.C, dtype=o.dtype, device=o.device)
-    stats = torch.empty(d.M, 2, dtype=torch.float32, device=o.device)
+    ln_ptrs, out = _next_ln(d, o, next_ln)
     check(_lib.load().focal_mlp_proj_fwd(C.byref(d), _p(o), _p(x), _p(wp), _p(bp), C.byref(mask), _p(g2), _p(bt2), _p(x_mid), _p(a2), _p(st2), _p(w1), _p(b1),
-                                         _p(w2), _p(b2), _p(y), _p(next_ln[0]), _p(next_ln[1]), _p(y_ln), _p(stats), _p(mask_bits), _stream()))
-    return (a2, st2), (y_ln, stats)
+                                         _p(w2), _p(b2), _p(y), *ln_ptrs, _p(mask_bits), _stream()))
+    return (a2, st2), out
 
 
 def mlp_wide_supported(dtype, Cc, hidden):
@@ -585,14 +589,9 @@ def mlp_wide_fwd(d, a, resid, w1, b1, w2, b2, y, h, hg, next_ln=None):
     returns (LayerNorm(y) in a's dtype, stats).  Bit-identical to linear_fwd(GELU) + linear_fwd / linear_resid_ln_fwd."""
     _need_cuda(a, resid, w1, b1, w2, b2, y, h, hg)
     assert h.shape == (d.M, d.hidden) and hg.shape == h.shape and h.dtype == a.dtype and hg.dtype == a.dtype and h.is_contiguous() and hg.is_contiguous()
-    if next_ln is None:
-        check(_lib.load().focal_mlp_wide_fwd(C.byref(d), _p(a), _p(resid), _p(w1), _p(b1), _p(w2), _p(b2), _p(y), _p(h), _p(hg), None, None, None, None, _stream()))
-        return None
-    y_ln = torch.empty(d.M, d.C, dtype=a.dtype, device=a.device)
-    stats = torch.empty(d.M, 2, dtype=torch.float32, device=a.device)
-    check(_lib.load().focal_mlp_wide_fwd(C.byref(d), _p(a), _p(resid), _p(w1), _p(b1), _p(w2), _p(b2), _p(y), _p(h), _p(hg), _p(next_ln[0]), _p(next_ln[1]),
-                                         _p(y_ln), _p(stats), _stream()))
-    return y_ln, stats
+    ln_ptrs, out = _next_ln(d, a, next_ln)
+    check(_lib.load().focal_mlp_wide_fwd(C.byref(d), _p(a), _p(resid), _p(w1), _p(b1), _p(w2), _p(b2), _p(y), _p(h), _p(hg), *ln_ptrs, _stream()))
+    return out
 
 
 def mlp_wide_proj_supported(dtype, Cc, hidden):
@@ -606,15 +605,10 @@ def mlp_wide_proj_fwd(d, o, x, wp, bp, drop_proj, g2, bt2, x_mid, w1, b1, w2, b2
     a2 = torch.empty(d.M, d.C, dtype=o.dtype, device=o.device)
     st2 = torch.empty(d.M, 2, dtype=torch.float32, device=o.device)
     mask = drop_proj or NO_DROP
-    if next_ln is None:
-        check(_lib.load().focal_mlp_wide_proj_fwd(C.byref(d), _p(o), _p(x), _p(wp), _p(bp), C.byref(mask), _p(g2), _p(bt2), _p(x_mid), _p(a2), _p(st2), _p(w1), _p(b1),
-                                                  _p(w2), _p(b2), _p(y), _p(h), _p(hg), None, None, None, None, _stream()))
-        return (a2, st2), None
-    y_ln = torch.empty(d.M, d.C, dtype=o.dtype, device=o.device)
-    stats = torch.empty(d.M, 2, dtype=torch.float32, device=o.device)
+    ln_ptrs, out = _next_ln(d, o, next_ln)
     check(_lib.load().focal_mlp_wide_proj_fwd(C.byref(d), _p(o), _p(x), _p(wp), _p(bp), C.byref(mask), _p(g2), _p(bt2), _p(x_mid), _p(a2), _p(st2), _p(w1), _p(b1),
-                                              _p(w2), _p(b2), _p(y), _p(h), _p(hg), _p(next_ln[0]), _p(next_ln[1]), _p(y_ln), _p(stats), _stream()))
-    return (a2, st2), (y_ln, stats)
+                                              _p(w2), _p(b2), _p(y), _p(h), _p(hg), *ln_ptrs, _stream()))
+    return (a2, st2), out
 
 
 def mlp_wide_bwd_supported(dtype, Cc, hidden):
@@ -628,11 +622,10 @@ def mlp_wide_bwd_data(d, gm, hg, w1, w2, du, dc=None, ln=None):
     assert du.shape == (d.M, d.hidden) and du.dtype == gm.dtype and du.is_contiguous() and hg.shape == du.shape
     if ln is None:
         assert dc is not None and dc.shape == (d.M, d.C) and dc.dtype == gm.dtype and dc.is_contiguous()
-        check(_lib.load().focal_mlp_wide_bwd_data(C.byref(d), _p(gm), _p(hg), _p(w1), _p(w2), _p(du), _p(dc), None, None, None, None, None, None, None, None, _stream()))
-        return
-    mask = ln.get("mask") or NO_DROP
-    check(_lib.load().focal_mlp_wide_bwd_data(C.byref(d), _p(gm), _p(hg), _p(w1), _p(w2), _p(du), None, _p(ln["x"]), _p(ln["stats"]), _p(ln["gamma"]), _p(ln["g"]),
-                                              _p(ln.get("g_masked")), C.byref(mask), _p(ln["dgamma"]), _p(ln["dbeta"]), _stream()))
+    L = ln or {}  # (with ln the row's LayerNorm backward replaces dc: the kernel gets no dc pointer; without it no mask pointer)
+    check(_lib.load().focal_mlp_wide_bwd_data(C.byref(d), _p(gm), _p(hg), _p(w1), _p(w2), _p(du), _p(dc if ln is None else None), _p(L.get("x")), _p(L.get("stats")),
+                                              _p(L.get("gamma")), _p(L.get("g")), _p(L.get("g_masked")), _ln_mask(ln, "mask"), _p(L.get("dgamma")),
+                                              _p(L.get("dbeta")), _stream()))
 
 
 def mlp_bwd_partials_floats(d):
@@ -650,14 +643,10 @@ def mlp_bwd(d, gm, a, w1, b1, w2, da, dw1, db1, dw2, db2, ln=None, mask_bits=Non
     gm_next = dtype(g x next_mask), dgamma / dbeta accumulate, and `da` is neither needed nor written (pass None) -- what the Swin engine
     always does.  partials (mlp_bwd_partials): the weight gradients leave through a workspace + a reduce launch instead of atomics."""
     _need_cuda(gm, a, w1, b1, w2, da, dw1, db1, dw2, db2, mask_bits, partials)
-    if ln is None:
-        check(_lib.load().focal_mlp_bwd(C.byref(d), _p(gm), _p(a), _p(w1), _p(b1), _p(w2), _p(da), _p(dw1), _p(db1), _p(dw2), _p(db2),
-                                        None, None, None, None, None, None, None, None, _p(mask_bits), _p(partials), _stream()))
-        return
-    mask = ln.get("next_mask") or NO_DROP
+    L = ln or {}
     check(_lib.load().focal_mlp_bwd(C.byref(d), _p(gm), _p(a), _p(w1), _p(b1), _p(w2), _p(da), _p(dw1), _p(db1), _p(dw2), _p(db2),
-                                    _p(ln["x"]), _p(ln["stats"]), _p(ln["gamma"]), _p(ln["g"]), _p(ln.get("gm_next")), C.byref(mask),
-                                    _p(ln["dgamma"]), _p(ln["dbeta"]), _p(mask_bits), _p(partials), _stream()))
+                                    _p(L.get("x")), _p(L.get("stats")), _p(L.get("gamma")), _p(L.get("g")), _p(L.get("gm_next")), _ln_mask(ln, "next_mask"),
+                                    _p(L.get("dgamma")), _p(L.get("dbeta")), _p(mask_bits), _p(partials), _stream()))
 
 
 # ------------------------------------------------------------------------------------------------ row 10

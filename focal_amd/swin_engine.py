@@ -11,6 +11,7 @@ Per block (M = B*H*W tokens, C channels, CT = matrix-core operand dtype):
   backward  the residual-gradient stream g (fp32 [M, C]) is updated in place through the block.
 """
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -40,6 +41,76 @@ def tail_weight(bb, ar, name, which="mod_in"):
     return ar.master(name) if tail_fp32(bb, which) else ar.operand(name)
 
 
+class BlockPlan(NamedTuple):
+    """Which form each part of one Swin block takes (plan_block); forward stores it in the block's saved record, backward follows it."""
+    attn_qkv: bool  # the attention kernel projects q / k / v itself: no qkv GEMM, no [M, 3C] tensor
+    mlp: str        # "fused" (one kernel, hidden activation never in HBM) | "wide" (one launch, h / hg written once) | "plain" (fc1, fc2)
+    proj: str       # proj + residual + norm2: "in_mlp" (in front of the MLP, in its launch) | "resid_ln" (one GEMM with the LayerNorm epilogue) | "plain"
+    next_ln: bool   # the MLP / fc2 launch also emits the next block's norm1
+    mlp_bwd: str    # "fused" (mlp_bwd) | "wide" (mlp_wide_bwd_data) | "plain" (two dX GEMMs)
+    ln2_bwd: str    # norm2's backward: "mlp" (epilogue of the MLP backward) | "dx" (epilogue of fc1's dX GEMM) | "plain"
+    ln1_bwd: str    # norm1's backward: "dx" (epilogue of qkv's dX GEMM) | "plain"
+    dw_group: int   # the block's stand-alone weight gradients: 0 one launch each | 1 one launch of 64 x 64 ring tiles | 2 one launch of 128 x 128 tiles
+
+
+def plan_block(ct, M, Cc, heads, window_tokens, has_next):
+    """The forms of one block of `M` tokens x `Cc` channels in compute dtype `ct`; `has_next`: another block of the stage follows.  Every
+    choice is made here and nowhere else.  Not to be cached across calls: the library's *_supported queries read their FOCAL_* switches
+    per call.  LayerNorm forwards ride on their producers and the MLP branch is one kernel wherever the library has the kernel for the
+    dtype / shape (the exact-fp32 mode runs the plain kernels)."""
+    cc = ops.code(ct)
+    hidden = 4 * Cc
+    # The LayerNorm epilogue of the residual GEMMs beyond 64 channels (row-complete wave tiles on the LDS-DMA GEMM): at 128 channels
+    # (+1.1 % on the step, same-box), not at 256, where one row fragment per wave makes the fused fc2 take 55-61 us against 35 + 11
+    # (-1 % with both on; profiles/r3_ln_wide_ab.txt).
+    ln_epilogue = Cc <= 128
+    # 64-channel blocks: the attention kernel projects q / k / v of a (window, head) item itself -- no qkv GEMM launch, no [M, 3C] tensor
+    # written, read back or saved (the backward kernel recomputes it from a1)
+    attn_qkv = bool(ops.attn_qkv_supported(cc, Cc, heads, window_tokens))
+    # The MLP is ONE choice, and only the chosen kind's proj form is asked for.  64-channel blocks: the whole branch in one kernel, the
+    # [M, 4C] hidden activation never reaches HBM and is recomputed in backward.  Stages 1-2 (round 6): fc1 -> GELU -> dropout -> fc2 ->
+    # residual as ONE launch; h and hg are written once for the backward pass and never read back (bit-identical to the two launches).
+    # Round 6: proj + residual + norm2 ride in FRONT of either, in its launch (ops.mlp_proj_fwd / ops.mlp_wide_proj_fwd).
+    if ops.mlp_supported(ct, Cc, hidden):
+        mlp, proj_in_mlp = "fused", ops.mlp_proj_supported(ct, Cc, hidden)
+    elif ops.mlp_wide_supported(ct, Cc, hidden):
+        mlp, proj_in_mlp = "wide", ops.mlp_wide_proj_supported(ct, Cc, hidden)
+    else:
+        mlp, proj_in_mlp = "plain", False
+    # Where a GEMM wave owns whole rows (64 channels: the 64 x 64 tile; 128 channels in bf16: the LDS-DMA kernel with row-complete wave
+    # tiles) the residual GEMMs also emit the LayerNorm that follows them (norm2 after proj, the next block's norm1 after fc2): no
+    # separate pass over the residual stream for those LayerNorms.
+    if proj_in_mlp:
+        proj = "in_mlp"
+    elif ln_epilogue and ops.resid_ln_supported(cc, Cc, Cc):
+        proj = "resid_ln"
+    else:
+        proj = "plain"
+    # (the one-launch MLPs emit the next norm1 at 256 channels too: a wave of the wide kernel owns whole rows, and its LayerNorm repeats
+    # ln_fwd_kernel's summation tree -- the next block's norm1 comes out bit-identical to the stand-alone launch it replaces)
+    next_ln = has_next and (mlp != "plain" or (ln_epilogue and bool(ops.resid_ln_supported(cc, Cc, hidden))))
+    # Stages 1-2 (round 6, FOCAL_MLP_WIDE_BWD=1; off by default: it does not pay inside the step): du = (gm W2) x h' and dL/da2 = du W1
+    # as ONE launch -- du is written once for fc1's weight gradient and feeds the second product from registers.
+    mlp_bwd = "fused" if mlp == "fused" else "wide" if ops.mlp_wide_bwd_supported(ct, Cc, hidden) else "plain"
+    # LayerNorm backward as the epilogue of the dX GEMM in front of it (64 / 128 channels, bf16): focal_linear_bwd_data_ln; at 256
+    # channels neither one nor two waves per row gained anything (profiles/r3_ln_bwd_fused_ab.txt; measured again in round 6).  The
+    # fused MLP backward always finishes norm2 itself; the wide one does where the dX epilogue would (its launcher rejects ln= beyond 128).
+    ln_bwd_epilogue = ct == torch.bfloat16 and Cc <= 128
+    want_ln2 = ln_bwd_epilogue and bool(ops.bwd_data_ln_supported(cc, hidden, Cc))
+    if mlp_bwd == "fused" or (mlp_bwd == "wide" and want_ln2):
+        ln2_bwd = "mlp"
+    else:
+        ln2_bwd = "dx" if want_ln2 else "plain"
+    ln1_bwd = "dx" if ln_bwd_epilogue and ops.bwd_data_ln_supported(cc, 3 * Cc, Cc) else "plain"
+    # The weight gradients of a block (proj, qkv and -- unless the fused MLP backward produces them -- fc2, fc1) as ONE launch once all
+    # their operands exist (ops.linear_bwd_weight_group).  Stages 1-2 (C >= 128): 128 x 128 tiles, one ramp and one atomic epilogue
+    # instead of four, half the L2 -> LDS bytes per MAC (kind 2).  64-channel blocks are too narrow for those tiles: one launch of the
+    # 64 x 64 ring tiles behind a problem table (kind 1).
+    shapes = [(Cc, Cc), (3 * Cc, Cc)] + ([] if mlp == "fused" else [(Cc, hidden), (hidden, Cc)])
+    dw_group = min(ops.dw_group_kind(cc, M, n_, k_) for n_, k_ in shapes)
+    return BlockPlan(attn_qkv, mlp, proj, next_ln, mlp_bwd, ln2_bwd, ln1_bwd, dw_group)
+
+
 class SwinModEncoder:
     def __init__(self, backbone, loc, mod, mod_index):
         self.bb = backbone
@@ -64,13 +135,6 @@ class SwinModEncoder:
             x_freq = x_freq.float().contiguous()
         pe = f"patch_embed.{self.loc}.{self.mod}"
         P = bb.param  # cold parameters (frozen patch embedding) are read where they live
-        # LayerNorm forwards ride on their producers (fuse_ln) and the 64-channel MLP branch is one kernel (fuse_mlp) wherever the library
-        # has the kernel for the dtype / shape (ops.*_supported; the exact-fp32 mode runs the plain kernels).
-        # The LayerNorm epilogue of the residual GEMMs beyond 64 channels (row-complete wave tiles on the LDS-DMA GEMM): at 128 channels
-        # (+1.1 % on the step, same-box), not at 256, where one row fragment per wave makes the fused fc2 take 55-61 us against 35 + 11
-        # (-1 % with both on; profiles/r3_ln_wide_ab.txt).
-        fuse_ln = fuse_mlp = True
-        LN_FUSE_MAX_C = 128
         pre_ln = None  # (a1, st1) of the next block when the kernel before it already produced them
         first = f"{self.pre}.0.blocks.0"
         embed_saved = None
@@ -86,7 +150,7 @@ class SwinModEncoder:
             z = ops.conv_in_fwd(d_pe, xpad, ar.master(f"{pe}.proj.weight"), ar.master(f"{pe}.proj.bias"))
             x, st_e = ops.layernorm_fwd(z, ar.master(f"{pe}.norm.weight"), ar.master(f"{pe}.norm.bias"), torch.float32)
             embed_saved = dict(d=d_pe, xpad=xpad, z=z, st=st_e)
-        elif fuse_ln and geo["stages"][0]["C"] == 64:  # the embedding kernel also emits block 0's norm1
+        elif geo["stages"][0]["C"] == 64:  # the embedding kernel also emits block 0's norm1
             x, a1_0, st1_0 = ops.pad_patch_embed_ln(x_freq, P(f"{pe}.proj.weight"), P(f"{pe}.proj.bias"), P(f"{pe}.norm.weight"),
                                                     P(f"{pe}.norm.bias"), geo["grid"][0], geo["grid"][1], geo["patch"][1],
                                                     next_ln=(ar.master(f"{first}.norm1.weight"), ar.master(f"{first}.norm1.bias"), ct))
@@ -100,9 +164,6 @@ class SwinModEncoder:
         p_attn = bb.attn_drop_rate if training else 0.0
         saved = {"B": B, "view": view, "training": training, "blocks": [], "merges": [], "embed": embed_saved}
         uid = 0
-        # Where a GEMM wave owns whole rows (64 channels: the 64 x 64 tile; 128 / 256 channels in bf16: the LDS-DMA kernel with
-        # row-complete wave tiles) the residual GEMMs also emit the LayerNorm that follows them (norm2 after proj, the next
-        # block's norm1 after fc2): no separate pass over the residual stream for those LayerNorms.
         for si, st in enumerate(geo["stages"]):
             H, W, Cc = st["H"], st["W"], st["C"]
             L = H * W
@@ -111,103 +172,79 @@ class SwinModEncoder:
                 pb = f"{self.pre}.{si}.blocks.{bi}"
                 wh, ww, sh, sw = bb.block_windows[(self.loc, self.mod, si, bi)]
                 p_path = bb.drop_path_rates[self.mod][uid] if training else 0.0
+                plan = plan_block(ct, M, Cc, geo["heads"], wh * ww, bi + 1 < st["depth"])
+                # ---- norm1, unless the kernel before this block already produced it
                 if pre_ln is not None:
                     a1, st1 = pre_ln
                     pre_ln = None
                 else:
                     a1, st1 = ops.layernorm_fwd(x, ar.master(f"{pb}.norm1.weight"), ar.master(f"{pb}.norm1.bias"), ct)
+                # ---- attention
                 d_qkv = ops.linear_desc(cc, M, 3 * Cc, Cc, cc, cc)
                 d_att = ops.attn_desc(cc, B, H, W, Cc, geo["heads"], wh, ww, sh, sw, p_attn, rng,
                                       ((view * 8 + self.mod_index) * 64 + uid) * 8 + 3)
                 o = torch.empty(M, Cc, dtype=ct, device=x.device)
-                if ops.attn_qkv_supported(cc, Cc, geo["heads"], wh * ww):
-                    # 64-channel blocks: the attention kernel projects q / k / v of a (window, head) item itself -- no qkv GEMM launch,
-                    # no [M, 3C] tensor written, read back or saved (the backward kernel recomputes it from a1)
-                    qkv = None
+                qkv = None
+                if plan.attn_qkv:
                     ops.window_attn_qkv_fwd(d_att, a1, ar.operand(f"{pb}.attn.qkv.weight"), ar.master(f"{pb}.attn.qkv.bias"),
                                             ar.master(f"{pb}.attn.relative_position_bias_table"), o)
                 else:
                     qkv = torch.empty(M, 3 * Cc, dtype=ct, device=x.device)
                     ops.linear_fwd(d_qkv, a1, ar.operand(f"{pb}.attn.qkv.weight"), ar.master(f"{pb}.attn.qkv.bias"), None, qkv)
                     ops.window_attn_fwd(d_att, qkv, ar.master(f"{pb}.attn.relative_position_bias_table"), o)
+                # ---- proj + residual + norm2 (plan.proj == "in_mlp": in the MLP's launch below)
                 d_proj = ops.linear_desc(cc, M, Cc, Cc, cc, f32, ACT_NONE, EPI_RESIDUAL,
                                          out_drop=self._drop(rng, view, uid, 0, p_drop, p_path, L))
                 x_mid = torch.empty(M, Cc, dtype=torch.float32, device=x.device)
-                fuse_wide = Cc <= LN_FUSE_MAX_C
-                # 64-channel blocks (round 6): proj + residual + norm2 ride in FRONT of the fused MLP, in its launch (ops.mlp_proj_fwd below)
-                proj_in_mlp = fuse_ln and fuse_mlp and ops.mlp_supported(ct, Cc, 4 * Cc) and ops.mlp_proj_supported(ct, Cc, 4 * Cc)
-                # ... and so do the 128 / 256-channel ones in front of the one-launch MLP of stages 1-2 (ops.mlp_wide_proj_fwd)
-                proj_in_wide = fuse_ln and fuse_mlp and ops.mlp_wide_supported(ct, Cc, 4 * Cc) and ops.mlp_wide_proj_supported(ct, Cc, 4 * Cc)
-                if proj_in_mlp or proj_in_wide:
-                    a2 = st2 = None
-                elif fuse_ln and (Cc == 64 or fuse_wide) and ops.resid_ln_supported(cc, Cc, Cc):
-                    a2, st2 = ops.linear_resid_ln_fwd(d_proj, o, ar.operand(f"{pb}.attn.proj.weight"), ar.master(f"{pb}.attn.proj.bias"),
-                                                      x, x_mid, ar.master(f"{pb}.norm2.weight"), ar.master(f"{pb}.norm2.bias"), ct)
-                else:
-                    ops.linear_fwd(d_proj, o, ar.operand(f"{pb}.attn.proj.weight"), ar.master(f"{pb}.attn.proj.bias"), x, x_mid)
-                    a2, st2 = ops.layernorm_fwd(x_mid, ar.master(f"{pb}.norm2.weight"), ar.master(f"{pb}.norm2.bias"), ct)
+                proj_w = (ar.operand(f"{pb}.attn.proj.weight"), ar.master(f"{pb}.attn.proj.bias"))
+                norm2_w = (ar.master(f"{pb}.norm2.weight"), ar.master(f"{pb}.norm2.bias"))
+                a2 = st2 = None
+                if plan.proj == "resid_ln":
+                    a2, st2 = ops.linear_resid_ln_fwd(d_proj, o, *proj_w, x, x_mid, *norm2_w, ct)
+                elif plan.proj == "plain":
+                    ops.linear_fwd(d_proj, o, *proj_w, x, x_mid)
+                    a2, st2 = ops.layernorm_fwd(x_mid, *norm2_w, ct)
+                # ---- MLP + residual (+ the next block's norm1)
                 d_fc1 = ops.linear_desc(cc, M, 4 * Cc, Cc, cc, cc, ACT_NONE, EPI_GELU,
                                         out_drop=self._drop(rng, view, uid, 1, p_drop, 0.0, L))
                 d_fc2 = ops.linear_desc(cc, M, Cc, 4 * Cc, cc, f32, ACT_GELU, EPI_RESIDUAL,
                                         out_drop=self._drop(rng, view, uid, 2, p_drop, p_path, L))
                 x_out = torch.empty(M, Cc, dtype=torch.float32, device=x.device)
-                d_mlp = h = hg = None
-                if fuse_mlp and ops.mlp_supported(ct, Cc, 4 * Cc):
-                    # the whole MLP branch in one kernel: the [M, 4C] hidden activation never reaches HBM and is recomputed in backward
-                    d_mlp = ops.mlp_desc(cc, M, Cc, 4 * Cc, d_fc1.out_drop, d_fc2.out_drop)
-                    nxt_ln = None
-                    if fuse_ln and bi + 1 < st["depth"]:
-                        nb = f"{self.pre}.{si}.blocks.{bi + 1}"
-                        nxt_ln = (ar.master(f"{nb}.norm1.weight"), ar.master(f"{nb}.norm1.bias"))
-                    mlp_bits = ops.mlp_mask_bits(d_mlp, x.device)  # the hidden dropout's keep bits (32 B per token): all the branch saves beside a2
-                    if proj_in_mlp:
-                        (a2, st2), pre_ln = ops.mlp_proj_fwd(d_mlp, o, x, ar.operand(f"{pb}.attn.proj.weight"), ar.master(f"{pb}.attn.proj.bias"), d_proj.out_drop,
-                                                             ar.master(f"{pb}.norm2.weight"), ar.master(f"{pb}.norm2.bias"), x_mid,
-                                                             ar.operand(f"{pb}.mlp.fc1.weight"), ar.master(f"{pb}.mlp.fc1.bias"),
-                                                             ar.operand(f"{pb}.mlp.fc2.weight"), ar.master(f"{pb}.mlp.fc2.bias"), x_out, next_ln=nxt_ln, mask_bits=mlp_bits)
-                    else:
-                        pre_ln = ops.mlp_fwd(d_mlp, a2, x_mid, ar.operand(f"{pb}.mlp.fc1.weight"), ar.master(f"{pb}.mlp.fc1.bias"),
-                                             ar.operand(f"{pb}.mlp.fc2.weight"), ar.master(f"{pb}.mlp.fc2.bias"), x_out, next_ln=nxt_ln, mask_bits=mlp_bits)
-                    saved["blocks"].append(dict(pb=pb, x=x, st1=st1, a1=a1, qkv=qkv, o=o, x_mid=x_mid, st2=st2, a2=a2, h=None, hg=None, mlp_bits=mlp_bits,
-                                                d_qkv=d_qkv, d_att=d_att, d_proj=d_proj, d_fc1=d_fc1, d_fc2=d_fc2, d_mlp=d_mlp, M=M, C=Cc))
-                    x = x_out
-                    uid += 1
-                    continue
-                h = torch.empty(M, 4 * Cc, dtype=ct, device=x.device)
-                hg = torch.empty(M, 4 * Cc, dtype=ct, device=x.device)  # d h / d(pre-activation), dropout included
-                want_ln = fuse_ln and (Cc == 64 or fuse_wide) and ops.resid_ln_supported(cc, Cc, 4 * Cc) and bi + 1 < st["depth"]
-                if fuse_mlp and ops.mlp_wide_supported(ct, Cc, 4 * Cc):
-                    # stages 1-2 (round 6): fc1 -> GELU -> dropout -> fc2 -> residual (+ the next LayerNorm at 128 channels) as ONE launch; h and
-                    # hg are written once for the backward pass and never read back (bit-identical to the two launches below)
-                    d_wide = ops.mlp_desc(cc, M, Cc, 4 * Cc, d_fc1.out_drop, d_fc2.out_drop)
-                    nxt_ln = None
-                    if want_ln or (fuse_ln and bi + 1 < st["depth"] and os.environ.get("FOCAL_MLP_WIDE_LN256") != "0"):
-                        # (256 channels too: a wave of this kernel owns whole rows, and its LayerNorm repeats ln_fwd_kernel's summation tree --
-                        # the next block's norm1 comes out bit-identical to the stand-alone launch it replaces)
-                        nb = f"{self.pre}.{si}.blocks.{bi + 1}"
-                        nxt_ln = (ar.master(f"{nb}.norm1.weight"), ar.master(f"{nb}.norm1.bias"))
-                    if proj_in_wide:
-                        (a2, st2), pre_ln = ops.mlp_wide_proj_fwd(d_wide, o, x, ar.operand(f"{pb}.attn.proj.weight"), ar.master(f"{pb}.attn.proj.bias"), d_proj.out_drop,
-                                                                  ar.master(f"{pb}.norm2.weight"), ar.master(f"{pb}.norm2.bias"), x_mid,
-                                                                  ar.operand(f"{pb}.mlp.fc1.weight"), ar.master(f"{pb}.mlp.fc1.bias"),
-                                                                  ar.operand(f"{pb}.mlp.fc2.weight"), ar.master(f"{pb}.mlp.fc2.bias"), x_out, h, hg, next_ln=nxt_ln)
-                    else:
-                        pre_ln = ops.mlp_wide_fwd(d_wide, a2, x_mid, ar.operand(f"{pb}.mlp.fc1.weight"), ar.master(f"{pb}.mlp.fc1.bias"),
-                                                  ar.operand(f"{pb}.mlp.fc2.weight"), ar.master(f"{pb}.mlp.fc2.bias"), x_out, h, hg, next_ln=nxt_ln)
-                    saved["blocks"].append(dict(pb=pb, x=x, st1=st1, a1=a1, qkv=qkv, o=o, x_mid=x_mid, st2=st2, a2=a2, h=h, hg=hg,
-                                                d_qkv=d_qkv, d_att=d_att, d_proj=d_proj, d_fc1=d_fc1, d_fc2=d_fc2, M=M, C=Cc))
-                    x = x_out
-                    uid += 1
-                    continue
-                ops.linear_fwd(d_fc1, a2, ar.operand(f"{pb}.mlp.fc1.weight"), ar.master(f"{pb}.mlp.fc1.bias"), None, h, hg)
-                if fuse_ln and (Cc == 64 or fuse_wide) and ops.resid_ln_supported(cc, Cc, 4 * Cc) and bi + 1 < st["depth"]:
+                mlp_w = (ar.operand(f"{pb}.mlp.fc1.weight"), ar.master(f"{pb}.mlp.fc1.bias"),
+                         ar.operand(f"{pb}.mlp.fc2.weight"), ar.master(f"{pb}.mlp.fc2.bias"))
+                nxt_ln = None
+                if plan.next_ln:
                     nb = f"{self.pre}.{si}.blocks.{bi + 1}"
-                    pre_ln = ops.linear_resid_ln_fwd(d_fc2, h, ar.operand(f"{pb}.mlp.fc2.weight"), ar.master(f"{pb}.mlp.fc2.bias"),
-                                                     x_mid, x_out, ar.master(f"{nb}.norm1.weight"), ar.master(f"{nb}.norm1.bias"), ct)
+                    nxt_ln = (ar.master(f"{nb}.norm1.weight"), ar.master(f"{nb}.norm1.bias"))
+                # (the plan names "in_mlp" only for an MLP kind that has the proj form; every other proj form has produced norm2 above)
+                assert plan.proj == "in_mlp" or (a2 is not None and st2 is not None)
+                d_mlp = h = hg = mlp_bits = None
+                if plan.mlp == "fused":
+                    d_mlp = ops.mlp_desc(cc, M, Cc, 4 * Cc, d_fc1.out_drop, d_fc2.out_drop)
+                    mlp_bits = ops.mlp_mask_bits(d_mlp, x.device)  # the hidden dropout's keep bits (32 B per token): all the branch saves beside a2
+                    if plan.proj == "in_mlp":
+                        (a2, st2), pre_ln = ops.mlp_proj_fwd(d_mlp, o, x, *proj_w, d_proj.out_drop, *norm2_w, x_mid, *mlp_w, x_out,
+                                                             next_ln=nxt_ln, mask_bits=mlp_bits)
+                    else:
+                        pre_ln = ops.mlp_fwd(d_mlp, a2, x_mid, *mlp_w, x_out, next_ln=nxt_ln, mask_bits=mlp_bits)
                 else:
-                    ops.linear_fwd(d_fc2, h, ar.operand(f"{pb}.mlp.fc2.weight"), ar.master(f"{pb}.mlp.fc2.bias"), x_mid, x_out)
-                saved["blocks"].append(dict(pb=pb, x=x, st1=st1, a1=a1, qkv=qkv, o=o, x_mid=x_mid, st2=st2, a2=a2, h=h, hg=hg,
-                                            d_qkv=d_qkv, d_att=d_att, d_proj=d_proj, d_fc1=d_fc1, d_fc2=d_fc2,
+                    h = torch.empty(M, 4 * Cc, dtype=ct, device=x.device)
+                    hg = torch.empty(M, 4 * Cc, dtype=ct, device=x.device)  # d h / d(pre-activation), dropout included
+                    if plan.mlp == "wide":
+                        d_mlp = ops.mlp_desc(cc, M, Cc, 4 * Cc, d_fc1.out_drop, d_fc2.out_drop)
+                        if plan.proj == "in_mlp":
+                            (a2, st2), pre_ln = ops.mlp_wide_proj_fwd(d_mlp, o, x, *proj_w, d_proj.out_drop, *norm2_w, x_mid, *mlp_w, x_out, h, hg,
+                                                                      next_ln=nxt_ln)
+                        else:
+                            pre_ln = ops.mlp_wide_fwd(d_mlp, a2, x_mid, *mlp_w, x_out, h, hg, next_ln=nxt_ln)
+                    else:
+                        ops.linear_fwd(d_fc1, a2, *mlp_w[:2], None, h, hg)
+                        if nxt_ln is not None:
+                            pre_ln = ops.linear_resid_ln_fwd(d_fc2, h, *mlp_w[2:], x_mid, x_out, *nxt_ln, ct)
+                        else:
+                            ops.linear_fwd(d_fc2, h, *mlp_w[2:], x_mid, x_out)
+                saved["blocks"].append(dict(plan=plan, pb=pb, x=x, st1=st1, a1=a1, qkv=qkv, o=o, x_mid=x_mid, st2=st2, a2=a2, h=h, hg=hg,
+                                            mlp_bits=mlp_bits, d_qkv=d_qkv, d_att=d_att, d_proj=d_proj, d_fc1=d_fc1, d_fc2=d_fc2, d_mlp=d_mlp,
                                             M=M, C=Cc))
                 x = x_out
                 uid += 1
@@ -219,7 +256,8 @@ class SwinModEncoder:
                 d_red = ops.linear_desc(cc, M4, 2 * Cc, 4 * Cc, cc, f32)
                 x_next = torch.empty(M4, 2 * Cc, dtype=torch.float32, device=x.device)
                 ops.linear_fwd(d_red, a4, ar.operand(f"{pm}.reduction.weight"), None, None, x_next)
-                saved["merges"].append(dict(pm=pm, x=x, st4=st4, a4=a4, d_red=d_red, gather=gather, after_block=len(saved["blocks"])))
+                saved["merges"].append(dict(pm=pm, x=x, st4=st4, a4=a4, d_red=d_red, gather=gather, after_block=len(saved["blocks"]),
+                                             dw_group=ops.dw_group_kind(cc, d_red.M, d_red.N, d_red.K)))
                 x = x_next
         last = geo["stages"][-1]
         K = last["H"] * last["W"] * last["C"]
@@ -234,9 +272,7 @@ class SwinModEncoder:
 
     def _mlp_partials(self, d_mlp, dev):
         """Workspace of the fused MLP backward's weight-gradient flush (one per encoder: its blocks run one after the other on the
-        encoder's stream); FOCAL_MLP_BWD_ATOMICS=1 keeps the round-4 atomic flush (same-box A/B)."""
-        if os.environ.get("FOCAL_MLP_BWD_ATOMICS") == "1":
-            return None
+        encoder's stream)."""
         # one workspace per size, never dropped: a captured step graph holds its address, and a smaller batch later (the last one of an
         # epoch) followed by the captured shape again must find the block where the graph left it (ADVICE r5)
         pool = self.__dict__.setdefault("_mlp_ws", {})
@@ -283,7 +319,8 @@ class SwinModEncoder:
         self._backward_tail(saved, state)
 
     def _backward_blocks(self, saved, state, stop):
-        """Blocks state["next"] .. stop, last first; state carries the residual-stream gradient g and its masked operand copy gm."""
+        """Blocks state["next"] .. stop, last first; state carries the residual-stream gradient g and its masked operand copy gm.  Each
+        block runs the forms its saved plan names (plan_block)."""
         bb, ar = self.bb, self.bb.arena()
         ct = bb.compute_dtype
         g, gm = state["g"], state["gm"]
@@ -294,41 +331,20 @@ class SwinModEncoder:
         # gm = ct(g * mask): the residual-stream gradient times the dropout x drop-path mask of the branch that consumes it
         # next, written once by whichever kernel completes g (LayerNorm backward, or mask_cast for the first one); the
         # branch's dX / dW GEMMs then run as plain `ct` kernels instead of regenerating the mask per column tile.
-        group_dw = True
-        # LayerNorm backward as the epilogue of the dX GEMM in front of it (64 / 128 channels, bf16): focal_linear_bwd_data_ln; at 256
-        # channels neither one nor two waves per row gained anything (profiles/r3_ln_bwd_fused_ab.txt)
-        fuse_ln_bwd = ct == torch.bfloat16
-        ln_bwd_max_c = int(os.environ.get("FOCAL_LN_BWD_MAX_C", "128"))  # (256: measured again in round 6, tools/ab_env.sh)
         # one pass per step over this encoder's weights (both views in one batch): a gradient tile has a single writer per launch
         exclusive_dw = bool(getattr(bb, "views_share_pass", False))
         # (A block's weight gradients on a side stream -- nothing in the backward pass waits for them -- was measured in round 3 and lost
         # 9 % / 20 %: their operands must then outlive the block, and every later temporary lands on memory the Infinity Cache does not
-        # hold; profiles/r3_dw_stream_ab.txt.  The code was removed in round 4.)
-        # FOCAL_DW_PAIR = n > 1: the group launches of n consecutive blocks (128 x 128 tiles: stages 1-2) go out as ONE launch.  A launch costs
-        # ~8 us of ramp and ~8 us of memory-side fp32 atomics (one 64 KB tile per workgroup whatever the problem count: tools/lab_dwg.sh), and
-        # twice the tiles need half the token slices -- but 96 tiles x 144 ring stages cut into <= 256 workgroups is 2 slices of 72 stages
-        # (192 workgroups) against 5 of 29 (240), and the operands of the waiting block stay alive a block longer: measured -0.4 ... -0.9 % (2) and
-        # -0.9 ... +0.7 % (4) inside the step (tools/ab_dw_pair.sh, profiles/r6_dw_group_fixed_cost.txt).  NOT the default.
-        dw_pair = int(os.environ.get("FOCAL_DW_PAIR", "1"))
-        pending = state.setdefault("dw_pending", [])
+        # hold; profiles/r3_dw_stream_ab.txt.  The code was removed in round 4.  The group launches of n consecutive blocks as ONE launch
+        # keep the waiting block's operands alive a block longer and measured -0.9 ... +0.7 %: profiles/r6_dw_group_fixed_cost.txt;
+        # removed after round 6, DESIGN.md names the commit.)
+        dw_items = []  # the current block's grouped weight-gradient problems (dy, x, dw, dbias)
 
-        def flush_dw():
-            if pending:
-                ops.linear_bwd_weight_group(cc, list(pending), exclusive=exclusive_dw)
-                pending.clear()
-                state["dw_pending_blocks"] = 0
-
-        def submit_dw(items, mergeable):
-            """Launch a block's grouped weight gradients, or park them for the next block's launch; True when they are still waiting."""
-            if not mergeable or dw_pair <= 1:
-                ops.linear_bwd_weight_group(cc, items, exclusive=exclusive_dw)
-                return False
-            pending.extend(items)
-            state["dw_pending_blocks"] = state.get("dw_pending_blocks", 0) + 1
-            if state["dw_pending_blocks"] >= dw_pair or len(pending) + 5 > ops.DW_GROUP_MAX_PROBLEMS:
-                flush_dw()
-                return False
-            return True
+        def weight_grad(desc, dy, x, dw, db):
+            if plan.dw_group >= 1:  # they go out as one launch once all their operands exist
+                dw_items.append((dy, x, dw, db))
+            else:
+                ops.linear_bwd_weight(desc, dy, x, dw, db)
 
         for k in range(state["next"], stop - 1, -1):
             if (k + 1) in merges:  # a PatchMerging sits between block k and block k+1
@@ -347,76 +363,49 @@ class SwinModEncoder:
                                   ar.g(f"{pm}.norm.weight"), ar.g(f"{pm}.norm.bias"), gather=mg["gather"],
                                   dx_masked=gm, mask=blocks[k]["d_fc2"].out_drop)
             s = blocks[k]
-            pb, M, Cc = s["pb"], s["M"], s["C"]
+            plan, pb, M, Cc = s["plan"], s["pb"], s["M"], s["C"]
             gm = gm.view(M, Cc)
-            # The four weight gradients of a block (fc2, fc1, proj, qkv) as ONE launch on 128 x 128 tiles once all their operands
-            # exist (ops.linear_bwd_weight_group; stages 1-2: C >= 128): one ramp and one atomic epilogue instead of four, half the
-            # L2 -> LDS bytes per MAC.  Their operands stay alive until then, so the attention branch's masked gradient gets a buffer
-            # of its own instead of overwriting the MLP branch's.
-            # 64-channel blocks (stage 0) are too narrow for those tiles: their launches -- qkv and proj beside the fused MLP kernel, all four
-            # otherwise -- go out as one launch of the 64 x 64 ring tiles behind a problem table (dw_group_kind 1).
-            fused_mlp = s.get("d_mlp") is not None
-            shapes = [(Cc, Cc), (3 * Cc, Cc)] + ([] if fused_mlp else [(Cc, 4 * Cc), (4 * Cc, Cc)])
-            kinds = [ops.dw_group_kind(cc, M, n_, k_) for n_, k_ in shapes] if group_dw else [0]
-            grouped = min(kinds) >= 1
-            grouped128 = min(kinds) == 2
-            dw_items, dw_calls = [], []  # grouped problems / single launches (descriptor, dy, x, dw, dbias) of this block
-
-            def weight_grad(desc, dy, x, dw, db):
-                if grouped:
-                    dw_items.append((dy, x, dw, db))
-                else:
-                    ops.linear_bwd_weight(desc, dy, x, dw, db)
             # ---- MLP branch: x_out = x_mid + mask * (h W2^T + b2), h = drop(gelu(a2 W1^T + b1))
             dc = torch.empty_like(s["a2"])
             du = None
-            ln2_done = False
-            ln2_in_mlp = False
-            if fused_mlp:
-                # fused branch: h and h' recomputed from a2, all four parameter gradients from one pass -- and norm2's backward on the
-                # kernel's fp32 dL/da2: g += dLN, the attention branch's masked copy (written over gm: a tile's rows are read before
-                # they are written) and dgamma / dbeta come out of the same launch; no dL/da2 tensor, no LayerNorm-backward launch
-                ln2_in_mlp = True
-                ops.mlp_bwd(s["d_mlp"], gm, s["a2"], ar.operand(f"{pb}.mlp.fc1.weight"), ar.master(f"{pb}.mlp.fc1.bias"),
-                            ar.operand(f"{pb}.mlp.fc2.weight"), None, ar.g(f"{pb}.mlp.fc1.weight"), ar.g(f"{pb}.mlp.fc1.bias"),
-                            ar.g(f"{pb}.mlp.fc2.weight"), ar.g(f"{pb}.mlp.fc2.bias"), mask_bits=s["mlp_bits"], partials=self._mlp_partials(s["d_mlp"], dev),
-                            ln=dict(x=s["x_mid"], stats=s["st2"], gamma=ar.master(f"{pb}.norm2.weight"), g=g, gm_next=gm,
-                                    next_mask=s["d_proj"].out_drop, dgamma=ar.g(f"{pb}.norm2.weight"), dbeta=ar.g(f"{pb}.norm2.bias")))
+            if plan.mlp_bwd == "fused":
+                partials = self._mlp_partials(s["d_mlp"], dev)  # (a first call allocates, and it does before gm_attn lets go of the last block's buffer)
             else:
                 d_fc2_b = ops.linear_desc(cc, M, Cc, 4 * Cc, cc, cc, ACT_GELU)  # dy = gm: operand dtype, already masked
                 weight_grad(d_fc2_b, gm, s["h"], ar.g(f"{pb}.mlp.fc2.weight"), ar.g(f"{pb}.mlp.fc2.bias"))
                 du = torch.empty_like(s["h"])
-                want_ln2 = fuse_ln_bwd and Cc <= ln_bwd_max_c and ops.bwd_data_ln_supported(cc, 4 * Cc, Cc)
-                if ops.mlp_wide_bwd_supported(ct, Cc, 4 * Cc):
-                    # stages 1-2 (round 6): du = (gm W2) x h' and dL/da2 = du W1 as ONE launch -- du is written once for fc1's weight gradient
-                    # and feeds the second product from registers; at 128 channels norm2's backward is the launch's epilogue, as it is
-                    # focal_linear_bwd_data_ln's
-                    d_wide = ops.mlp_desc(cc, M, Cc, 4 * Cc)
-                    if want_ln2:
-                        gm_attn = torch.empty_like(gm) if grouped else gm
-                        ops.mlp_wide_bwd_data(d_wide, gm, s["hg"], ar.operand(f"{pb}.mlp.fc1.weight"), ar.operand(f"{pb}.mlp.fc2.weight"), du,
-                                              ln=dict(x=s["x_mid"], stats=s["st2"], gamma=ar.master(f"{pb}.norm2.weight"), g=g, g_masked=gm_attn,
-                                                      mask=s["d_proj"].out_drop, dgamma=ar.g(f"{pb}.norm2.weight"), dbeta=ar.g(f"{pb}.norm2.bias")))
-                        ln2_in_mlp = True
-                    else:
-                        ops.mlp_wide_bwd_data(d_wide, gm, s["hg"], ar.operand(f"{pb}.mlp.fc1.weight"), ar.operand(f"{pb}.mlp.fc2.weight"), du, dc=dc)
-                    weight_grad(s["d_fc1"], du, s["a2"], ar.g(f"{pb}.mlp.fc1.weight"), ar.g(f"{pb}.mlp.fc1.bias"))
+            # The attention branch's masked gradient: where the MLP branch's gm is still an operand of the pending group launch it gets a
+            # buffer of its own; otherwise (the fused MLP backward has consumed gm, or its weight gradients are already out) it overwrites gm
+            gm_attn = torch.empty_like(gm) if (plan.mlp_bwd != "fused" and plan.dw_group >= 1) else gm
+            if plan.mlp_bwd == "fused":
+                # h and h' recomputed from a2, all four parameter gradients from one pass -- and norm2's backward on the kernel's fp32
+                # dL/da2: g += dLN, the attention branch's masked copy (written over gm: a tile's rows are read before they are written)
+                # and dgamma / dbeta come out of the same launch; no dL/da2 tensor, no LayerNorm-backward launch
+                ops.mlp_bwd(s["d_mlp"], gm, s["a2"], ar.operand(f"{pb}.mlp.fc1.weight"), ar.master(f"{pb}.mlp.fc1.bias"),
+                            ar.operand(f"{pb}.mlp.fc2.weight"), None, ar.g(f"{pb}.mlp.fc1.weight"), ar.g(f"{pb}.mlp.fc1.bias"),
+                            ar.g(f"{pb}.mlp.fc2.weight"), ar.g(f"{pb}.mlp.fc2.bias"), mask_bits=s["mlp_bits"], partials=partials,
+                            ln=dict(x=s["x_mid"], stats=s["st2"], gamma=ar.master(f"{pb}.norm2.weight"), g=g, gm_next=gm_attn,
+                                    next_mask=s["d_proj"].out_drop, dgamma=ar.g(f"{pb}.norm2.weight"), dbeta=ar.g(f"{pb}.norm2.bias")))
+            elif plan.mlp_bwd == "wide":
+                # du = (gm W2) x h' and dL/da2 = du W1 as one launch; with ln2_bwd == "mlp" norm2's backward is the launch's epilogue, as it
+                # is focal_linear_bwd_data_ln's
+                d_wide = ops.mlp_desc(cc, M, Cc, 4 * Cc)
+                if plan.ln2_bwd == "mlp":
+                    ops.mlp_wide_bwd_data(d_wide, gm, s["hg"], ar.operand(f"{pb}.mlp.fc1.weight"), ar.operand(f"{pb}.mlp.fc2.weight"), du,
+                                          ln=dict(x=s["x_mid"], stats=s["st2"], gamma=ar.master(f"{pb}.norm2.weight"), g=g, g_masked=gm_attn,
+                                                  mask=s["d_proj"].out_drop, dgamma=ar.g(f"{pb}.norm2.weight"), dbeta=ar.g(f"{pb}.norm2.bias")))
                 else:
-                    ops.linear_bwd_data(d_fc2_b, gm, ar.operand(f"{pb}.mlp.fc2.weight"), s["hg"], du)
-                    weight_grad(s["d_fc1"], du, s["a2"], ar.g(f"{pb}.mlp.fc1.weight"), ar.g(f"{pb}.mlp.fc1.bias"))
-                    if want_ln2:
-                        ln2_done = True  # dX of fc1 and norm2's backward in one kernel (below)
-                    else:
-                        ops.linear_bwd_data(s["d_fc1"], du, ar.operand(f"{pb}.mlp.fc1.weight"), None, dc)
-            # (the MLP branch's gm is still an operand of a pending weight gradient unless the fused branch has consumed it)
-            if not (ln2_in_mlp and not fused_mlp):
-                gm_attn = torch.empty_like(gm) if (not fused_mlp and grouped) else gm
-            if ln2_in_mlp:
-                pass
-            elif ln2_done:
+                    ops.mlp_wide_bwd_data(d_wide, gm, s["hg"], ar.operand(f"{pb}.mlp.fc1.weight"), ar.operand(f"{pb}.mlp.fc2.weight"), du, dc=dc)
+                weight_grad(s["d_fc1"], du, s["a2"], ar.g(f"{pb}.mlp.fc1.weight"), ar.g(f"{pb}.mlp.fc1.bias"))
+            else:
+                ops.linear_bwd_data(d_fc2_b, gm, ar.operand(f"{pb}.mlp.fc2.weight"), s["hg"], du)
+                weight_grad(s["d_fc1"], du, s["a2"], ar.g(f"{pb}.mlp.fc1.weight"), ar.g(f"{pb}.mlp.fc1.bias"))
+                if plan.ln2_bwd == "plain":
+                    ops.linear_bwd_data(s["d_fc1"], du, ar.operand(f"{pb}.mlp.fc1.weight"), None, dc)
+            if plan.ln2_bwd == "dx":  # dX of fc1 and norm2's backward in one kernel
                 ops.linear_bwd_data_ln(s["d_fc1"], du, ar.operand(f"{pb}.mlp.fc1.weight"), s["x_mid"], s["st2"], ar.master(f"{pb}.norm2.weight"), g,
                                        ar.g(f"{pb}.norm2.weight"), ar.g(f"{pb}.norm2.bias"), g_masked=gm_attn, mask=s["d_proj"].out_drop)
-            else:
+            elif plan.ln2_bwd == "plain":
                 ops.layernorm_bwd(dc, s["x_mid"], s["st2"], ar.master(f"{pb}.norm2.weight"), g, True,
                                   ar.g(f"{pb}.norm2.weight"), ar.g(f"{pb}.norm2.bias"), dx_masked=gm_attn, mask=s["d_proj"].out_drop)
             # ---- attention branch: x_mid = x + mask * (o Wp^T + bp)
@@ -426,7 +415,7 @@ class SwinModEncoder:
             dqkv = torch.empty(M, 3 * Cc, dtype=ct, device=dev)
             # (the branch's backward as ONE launch was built and measured in round 4 and is no faster inside the step: profiles/r4_attn_branch_bwd.txt,
             # tools/lab_attn_branch_bwd/)
-            if s["qkv"] is None:
+            if plan.attn_qkv:
                 # 64-channel blocks: q / k / v are recomputed from a1 inside the kernel (see forward), and so is the proj layer's input
                 # gradient -- the kernel forms its head's slice of gm_attn . Wproj per item: no dX launch, no dO tensor
                 ops.window_attn_qkv_bwd(s["d_att"], s["a1"], ar.operand(f"{pb}.attn.qkv.weight"), ar.master(f"{pb}.attn.qkv.bias"),
@@ -440,23 +429,21 @@ class SwinModEncoder:
             nxt = blocks[k - 1]["d_fc2"].out_drop if (k > 0 and k not in merges) else None
             weight_grad(s["d_qkv"], dqkv, s["a1"], ar.g(f"{pb}.attn.qkv.weight"), ar.g(f"{pb}.attn.qkv.bias"))
             da = do
-            ln1_fused = fuse_ln_bwd and Cc <= ln_bwd_max_c and ops.bwd_data_ln_supported(cc, 3 * Cc, Cc)
-            if not ln1_fused:
+            if plan.ln1_bwd == "plain":
                 ops.linear_bwd_data(s["d_qkv"], dqkv, ar.operand(f"{pb}.attn.qkv.weight"), None, da)
             # First block of a stage behind a PatchMerging: the merge's reduction linear takes this block's finished g as its dy.  With
             # a plain `ct` copy of g written by the LayerNorm backward below (as every other linear gets its dy), the reduction's weight
-            # gradient joins this block's group launch and its dX reads 2-byte operands.
-            mg_dw = merges.get(k) if grouped128 else None
-            if mg_dw is not None and ops.dw_group_kind(cc, mg_dw["d_red"].M, mg_dw["d_red"].N, mg_dw["d_red"].K) != 2:
+            # gradient joins this block's group launch (128 x 128 tiles on both sides) and its dX reads 2-byte operands.
+            mg_dw = merges.get(k) if plan.dw_group == 2 else None
+            if mg_dw is not None and mg_dw["dw_group"] != 2:
                 mg_dw = None
-            waiting = False
             if mg_dw is None and dw_items:
-                waiting = submit_dw(dw_items, grouped128)
+                ops.linear_bwd_weight_group(cc, dw_items, exclusive=exclusive_dw)
             du = None
             want_gm = nxt is not None or mg_dw is not None
-            if want_gm and (mg_dw is not None or waiting):
-                gm = torch.empty_like(gm)  # the old buffer is an operand of a group launch that has not run yet
-            if ln1_fused:  # dX of qkv and norm1's backward in one kernel
+            if mg_dw is not None:
+                gm = torch.empty_like(gm)  # the old buffer is an operand of the group launch, which has not run yet
+            if plan.ln1_bwd == "dx":  # dX of qkv and norm1's backward in one kernel
                 # the encoder's first block behind the frozen patch embedding: its input is a leaf nobody differentiates, so the
                 # residual-stream gradient stops here -- only norm1's dgamma / dbeta are produced (no read / update / re-cast of g)
                 g_out = None if (k == 0 and saved.get("embed") is None and not want_gm) else g
@@ -468,12 +455,11 @@ class SwinModEncoder:
                                   dx_masked=gm if want_gm else None, mask=nxt)
             if mg_dw is not None:
                 dw_items.append((gm.view(mg_dw["d_red"].M, mg_dw["d_red"].N), mg_dw["a4"], ar.g(f"{mg_dw['pm']}.reduction.weight"), None))
-                submit_dw(dw_items, True)
+                ops.linear_bwd_weight_group(cc, dw_items, exclusive=exclusive_dw)
                 mg_dw["dw_done"] = True
             del dqkv
             blocks[k] = None  # free this block's activations as we go
-            dw_items = dw_calls = weight_grad = None
-        flush_dw()
+            dw_items.clear()
         state.update(g=g, gm=gm, next=stop - 1)
 
     def _backward_tail(self, saved, state):

@@ -145,6 +145,38 @@ def test_encoder_with_the_one_launch_mlp_equals_the_default(cfg, monkeypatch):
     assert (g0 - g1).abs().max().item() <= 1e-2 * g0.abs().max().item()   # (observed 0.9e-3 .. 2.6e-3 over six runs)
 
 
+def test_encoder_with_proj_outside_the_mlp_launch_equals_the_default(cfg, monkeypatch):
+    """FOCAL_MLP_PROJ=0 through the Swin engine: proj + norm2 as their own launches (focal_linear_resid_ln_fwd at 64 / 128 channels, focal_linear_fwd +
+    focal_layernorm_fwd at 256) in front of focal_mlp_fwd / focal_mlp_wide_fwd, against the default where they ride in the MLP's launch.  The kernel-level
+    tests establish that the folded form is bit-identical with masks off, so the bounds are those of the test above: embeddings to the order of mod_in's
+    split-K atomics, gradients to the run-to-run noise of the bf16 backward."""
+    from test_swt_parity_gpu import build, inputs
+
+    def run():
+        args, net, focal, loss_fn = build(cfg, "bf16")
+        net.train()
+        x1, x2 = inputs(cfg)
+        f1, f2 = focal(x1, x2, proj_head=True)
+        loss = loss_fn(f1, f2)
+        net.arena().zero_grad()
+        loss.backward()
+        torch.cuda.synchronize()
+        return {m: f1[m].detach().clone() for m in f1}, net.arena().grad.clone()
+    from focal_amd import ops as o
+    monkeypatch.setenv("FOCAL_MLP_PROJ", "0")
+    assert not o.mlp_proj_supported(BF, 64, 256) and not o.mlp_wide_proj_supported(BF, 128, 512) and not o.mlp_wide_proj_supported(BF, 256, 1024)
+    e0, g0 = run()
+    monkeypatch.delenv("FOCAL_MLP_PROJ")
+    assert o.mlp_proj_supported(BF, 64, 256) and o.mlp_wide_proj_supported(BF, 128, 512) and o.mlp_wide_proj_supported(BF, 256, 1024)
+    e1, g1 = run()
+    emb = max(((e0[m] - e1[m]).abs().max() / e0[m].abs().max()).item() for m in e0)
+    grad = ((g0 - g1).abs().max() / g0.abs().max()).item()
+    print(f"FOCAL_MLP_PROJ=0 against the default: embeddings {emb:.3e} of scale, gradients {grad:.3e} of scale")
+    for m in e0:
+        assert (e0[m] - e1[m]).abs().max().item() <= 1e-5 * e0[m].abs().max().item()
+    assert (g0 - g1).abs().max().item() <= 1e-2 * g0.abs().max().item()
+
+
 @pytest.mark.parametrize("C,M,ln,drop", [(128, 36864, True, True), (128, 1000, True, False), (128, 96, False, False), (256, 9216, False, True), (256, 1000, False, False)])
 def test_backward_data_path_in_one_launch_equals_the_two_launches(ops, C, M, ln, drop):
     """focal_mlp_wide_bwd_data against focal_linear_bwd_data (GELU derivative) + focal_linear_bwd_data / focal_linear_bwd_data_ln: du, dc or
