@@ -52,6 +52,28 @@ class ViewPool(C.Structure):
                 ("intervals", C.c_int * VIEW_MAX_SLOTS)]
 
 
+# ---- jitter / channel shuffle / time mask / freq mask: additions beside the records above (include/focal_hip.h: focal_view_extra)
+VIEW_MAX_POOL_EX, VIEW_MAX_CHANNELS = 16, 16
+VIEW_JITTER, VIEW_CHANNEL_SHUFFLE, VIEW_TIME_MASK, VIEW_FREQ_MASK = 8, 9, 10, 11
+
+
+class ViewExtra(C.Structure):
+    _fields_ = [("jitter_std", C.c_float), ("jitter_key", C.c_uint32), ("use_chan", C.c_int), ("chan", C.c_int * VIEW_MAX_CHANNELS),
+                ("tmask_lo", C.c_int), ("tmask_n", C.c_int), ("fmask_lo", C.c_int), ("fmask_n", C.c_int)]
+
+
+class ViewPoolEx(C.Structure):
+    _fields_ = [("n_aug", C.c_int), ("kind", C.c_int * VIEW_MAX_POOL_EX), ("prob", C.c_float * VIEW_MAX_POOL_EX), ("scaling_std", C.c_float),
+                ("mag_magnitude", C.c_float), ("time_magnitude", C.c_float), ("mag_order", C.c_int), ("time_order", C.c_int),
+                ("intervals", C.c_int * VIEW_MAX_SLOTS), ("jitter_std", C.c_float * VIEW_MAX_SLOTS), ("channels", C.c_int * VIEW_MAX_SLOTS),
+                ("tmask_d", C.c_int * VIEW_MAX_SLOTS), ("tmask_i", C.c_int * VIEW_MAX_SLOTS), ("fmask_w", C.c_int * VIEW_MAX_SLOTS),
+                ("fmask_n", C.c_int * VIEW_MAX_SLOTS)]
+
+
+class FftProblemEx(C.Structure):
+    _fields_ = [("p", FftProblem), ("has_extra", C.c_int), ("extra", ViewExtra), ("extra_dev", C.c_void_p), ("noise_salt", C.c_uint32)]
+
+
 class WarpProblem(C.Structure):
     _fields_ = [("rows", C.c_int), ("L", C.c_int), ("x", C.c_void_p), ("plan", C.c_void_p), ("tables", C.c_void_p), ("y", C.c_void_p)]
 
@@ -142,6 +164,8 @@ PROTOTYPES = {
     "focal_warp_fwd": (C.c_int, [C.c_int, C.c_int, P, P, P, P, C.c_int, P, P]),
     "focal_view_draw": (C.c_int, [C.POINTER(ViewPool), C.c_int, C.c_int, P, C.c_uint32, P, P]),
     "focal_view_draw_shared": (C.c_int, [C.POINTER(ViewPool), C.c_int, C.c_int, P, C.c_uint32, P, P]),
+    "focal_view_draw_ex": (C.c_int, [C.POINTER(ViewPoolEx), C.c_int, C.c_int, P, C.c_int, C.c_uint32, P, P, P]),
+    "focal_fft_realpack_multi_ex": (C.c_int, [C.c_int, C.POINTER(FftProblemEx), P]),
     "focal_warp_plan_multi": (C.c_int, [C.c_int, C.POINTER(WarpProblem), P, P]),
     "focal_mixup_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
     "focal_pad_patch_embed_ln_fwd": (C.c_int, [C.POINTER(EmbedDesc), P, P, P, P, P, P, P]),

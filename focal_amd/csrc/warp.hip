@@ -78,8 +78,10 @@ __device__ __forceinline__ float vd_normal(uint32_t key, uint32_t i) {  // Box-M
 // `advance` (focal_view_draw_shared): the seed word is the draw's OWN state -- one every data-parallel rank holds a copy of, so that the global
 // batch gets one augmenter / coin / permutation / scale / phase per view as the reference's batch does -- and the kernel moves it on after
 // everybody has read it (the word the optimizer advances keys the per-rank dropout streams and stays per-rank).
-__global__ __launch_bounds__(64) void view_draw_kernel(const focal_view_pool pool, int n_views, int n_slots, uint32_t* seed,
-                                                       uint32_t stream_id, focal_view_plan* __restrict__ plans, int advance) {
+// (one body for both pool forms: EX = focal_view_pool_ex and an extras array -- the old kinds take the same draws and write the same bytes)
+template <class POOL, bool EX>
+__device__ __forceinline__ void view_draw_body(const POOL& pool, int n_views, int n_slots, uint32_t* seed, uint32_t stream_id,
+                                               focal_view_plan* __restrict__ plans, focal_view_extra* __restrict__ extras, int advance) {
   __shared__ int s_perm[64][FOCAL_AUG_MAX_INTERVALS + 1];
   const int t = threadIdx.x;
   const uint32_t s0 = seed ? seed[0] : 0u;
@@ -134,6 +136,55 @@ __global__ __launch_bounds__(64) void view_draw_kernel(const focal_view_pool poo
   pl->aug.scale = scale; pl->aug.flip = flip; pl->aug.use_perm = use_perm; pl->aug.phase_cos = pc; pl->aug.phase_sin = ps;
   for (int i = 0; i < FOCAL_AUG_MAX_INTERVALS; ++i) pl->aug.perm[i] = s_perm[t][i];
   pl->kind = kind; pl->pool_index = k; pl->warp = warp; pl->nknots = nk;
+  if constexpr (EX) {  // the four augmenters that travel in the extra record (include/focal_hip.h: draws 40 .. 63 of the slot key)
+    focal_view_extra* ex = extras + t;
+    float jstd = 0.f;
+    uint32_t jkey = 0u;
+    int use_chan = 0, tlo = 0, tn = 0, flo = 0, fn = 0;
+    int* chan = s_perm[t];  // (the plan's copy of the interval order has left: the row is free)
+    for (int i = 0; i < FOCAL_VIEW_MAX_CHANNELS; ++i) chan[i] = i;
+    if (kind == FOCAL_VIEW_JITTER) {
+      jstd = pool.jitter_std[slot];
+      jkey = focal_mix32(ks + 40u * 0x85EBCA6BU);
+    } else if (kind == FOCAL_VIEW_CHANNEL_SHUFFLE) {
+      use_chan = 1;
+      const int Cc = pool.channels[slot] < FOCAL_VIEW_MAX_CHANNELS ? pool.channels[slot] : FOCAL_VIEW_MAX_CHANNELS;
+      for (int i = Cc - 1; i > 0; --i) {
+        int j = (int)(vd_uniform(ks, 48 + i) * (float)(i + 1));
+        j = j <= i ? j : i;
+        const int a = chan[i];
+        chan[i] = chan[j];
+        chan[j] = a;
+      }
+    } else if (kind == FOCAL_VIEW_TIME_MASK) {
+      const int D = pool.tmask_d[slot], Iv = pool.tmask_i[slot];
+      int dur = 1 + (int)(vd_uniform(ks, 41) * (float)D);
+      dur = dur <= D ? dur : D;
+      int st = (int)(vd_uniform(ks, 42) * (float)(Iv - dur));
+      st = st < Iv - dur ? st : Iv - dur - 1;
+      tlo = st; tn = dur;
+    } else if (kind == FOCAL_VIEW_FREQ_MASK) {
+      const int W = pool.fmask_w[slot], nn = pool.fmask_n[slot];
+      int band = 1 + (int)(vd_uniform(ks, 43) * (float)W);
+      band = band <= W ? band : W;
+      int st = (int)(vd_uniform(ks, 44) * (float)(nn - band));
+      st = st < nn - band ? st : nn - band - 1;
+      flo = st; fn = band;
+    }
+    ex->jitter_std = jstd; ex->jitter_key = jkey; ex->use_chan = use_chan;
+    for (int i = 0; i < FOCAL_VIEW_MAX_CHANNELS; ++i) ex->chan[i] = use_chan ? chan[i] : 0;  // (an identity extra is all zero bytes)
+    ex->tmask_lo = tlo; ex->tmask_n = tn; ex->fmask_lo = flo; ex->fmask_n = fn;
+  }
+}
+
+__global__ __launch_bounds__(64) void view_draw_kernel(const focal_view_pool pool, int n_views, int n_slots, uint32_t* seed,
+                                                       uint32_t stream_id, focal_view_plan* __restrict__ plans, int advance) {
+  view_draw_body<focal_view_pool, false>(pool, n_views, n_slots, seed, stream_id, plans, nullptr, advance);
+}
+__global__ __launch_bounds__(64) void view_draw_ex_kernel(const focal_view_pool_ex pool, int n_views, int n_slots, uint32_t* seed,
+                                                          uint32_t stream_id, focal_view_plan* __restrict__ plans,
+                                                          focal_view_extra* __restrict__ extras, int advance) {
+  view_draw_body<focal_view_pool_ex, true>(pool, n_views, n_slots, seed, stream_id, plans, extras, advance);
 }
 
 static int view_draw_launch(const focal_view_pool* pool, int n_views, int n_slots, uint32_t* seed, uint32_t stream_id,
@@ -147,6 +198,32 @@ static int view_draw_launch(const focal_view_pool* pool, int n_views, int n_slot
     FOCAL_CHECK_ARG(ord >= 2 && 3 * (ord - 1) + 1 <= FOCAL_VIEW_MAX_KNOTS, "view_draw: spline order %d needs more than %d knots", ord, FOCAL_VIEW_MAX_KNOTS);
   }
   FOCAL_LAUNCH(view_draw_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *pool, n_views, n_slots, seed, stream_id, plans, advance);
+  FOCAL_LAUNCH_CHECK();
+  return FOCAL_OK;
+}
+
+extern "C" int focal_view_draw_ex(const focal_view_pool_ex* pool, int n_views, int n_slots, uint32_t* state, int advance, uint32_t stream_id,
+                                  focal_view_plan* plans, focal_view_extra* extras, void* stream) {
+  FOCAL_CHECK_ARG(pool && plans && extras && n_views >= 1 && n_slots >= 1 && n_slots <= FOCAL_VIEW_MAX_SLOTS && n_views * n_slots <= 64,
+                  "view_draw_ex: 1 .. %d slots, at most 64 (view, slot) pairs", FOCAL_VIEW_MAX_SLOTS);
+  FOCAL_CHECK_ARG(!advance || state != nullptr, "view_draw_ex: advance needs the view state (4 words: {seed, draw count, 0, 0})");
+  FOCAL_CHECK_ARG(pool->n_aug >= 1 && pool->n_aug <= FOCAL_VIEW_MAX_POOL_EX, "view_draw_ex: pool of 1 .. %d augmenters", FOCAL_VIEW_MAX_POOL_EX);
+  for (int i = 0; i < pool->n_aug; ++i) {
+    const int kd = pool->kind[i];
+    FOCAL_CHECK_ARG(kd >= FOCAL_VIEW_NONE && kd <= FOCAL_VIEW_FREQ_MASK, "view_draw_ex: unknown augmenter kind %d", kd);
+    const int ord = kd == FOCAL_VIEW_MAG_WARP ? pool->mag_order : kd == FOCAL_VIEW_TIME_WARP ? pool->time_order : 2;
+    FOCAL_CHECK_ARG(ord >= 2 && 3 * (ord - 1) + 1 <= FOCAL_VIEW_MAX_KNOTS, "view_draw_ex: spline order %d needs more than %d knots", ord, FOCAL_VIEW_MAX_KNOTS);
+    for (int s = 0; s < n_slots; ++s) {
+      if (kd == FOCAL_VIEW_JITTER) FOCAL_CHECK_ARG(pool->jitter_std[s] >= 0.f, "view_draw_ex: jitter std of slot %d is negative", s);
+      if (kd == FOCAL_VIEW_CHANNEL_SHUFFLE)
+        FOCAL_CHECK_ARG(pool->channels[s] >= 1 && pool->channels[s] <= FOCAL_VIEW_MAX_CHANNELS, "view_draw_ex: slot %d has %d channels (1 .. %d)", s, pool->channels[s], FOCAL_VIEW_MAX_CHANNELS);
+      if (kd == FOCAL_VIEW_TIME_MASK)
+        FOCAL_CHECK_ARG(pool->tmask_d[s] >= 1 && pool->tmask_i[s] - pool->tmask_d[s] >= 1, "view_draw_ex: time mask of slot %d needs D >= 1 and I - D >= 1 (D = %d, I = %d)", s, pool->tmask_d[s], pool->tmask_i[s]);
+      if (kd == FOCAL_VIEW_FREQ_MASK)
+        FOCAL_CHECK_ARG(pool->fmask_w[s] >= 2 && pool->fmask_n[s] - pool->fmask_w[s] >= 1, "view_draw_ex: freq mask of slot %d needs W >= 2 and n - W >= 1 (W = %d, n = %d)", s, pool->fmask_w[s], pool->fmask_n[s]);
+    }
+  }
+  FOCAL_LAUNCH(view_draw_ex_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *pool, n_views, n_slots, state, stream_id, plans, extras, advance ? 1 : 0);
   FOCAL_LAUNCH_CHECK();
   return FOCAL_OK;
 }

@@ -18,7 +18,8 @@ import logging
 import math
 import os
 import sys
-from random import random
+from math import floor
+from random import randint, random
 
 import numpy as np
 import torch
@@ -67,6 +68,29 @@ def _phase_shift(x, cfg):  # PhaseShiftAugmenter.py:39-54: rotate every complex 
     return dict(phase=(random() - 0.5) * 2 * math.pi)
 
 
+# The four augmenters whose parameters travel in a focal_view_extra (include/focal_hip.h).  Beside the dataset's own section `cfg` carries
+# what Augmenter.__init__ derived for the (location, modality) at hand: jitter "std", time_mask "max_duration", freq_mask "max_band_width".
+def _jitter(x, cfg):  # JitterAugmenter.py:37-40: x + N(0, 1) * std.  The reference draws the noise tensor; here one key, and the kernel the noise
+    return dict(jitter=(float(cfg["std"]), int(torch.randint(0, 2 ** 32, (1,), dtype=torch.int64).item())))
+
+
+def _channel_shuffle(x, cfg):  # ChannelShuffleAugmenter.py:34-37: one channel order for the whole batch
+    return dict(chan=torch.randperm(x.shape[1]).tolist())
+
+
+def _time_mask(x, cfg):  # TimeMaskAugmenter.py:37-41: interval-sized numbers, applied to the SAMPLE axis (sic); the slice clips at n
+    duration = randint(1, cfg["max_duration"])
+    start = torch.randint(0, x.shape[2] - duration, (1,)).item()
+    n = x.shape[3]
+    return dict(time_mask=(min(start, n), min(start + duration, n) - min(start, n)))
+
+
+def _freq_mask(x, cfg):  # FreqMaskAugmenter.py:44-48: a band of bins of all 2C channels, no mirror bin
+    band = randint(1, cfg["max_band_width"])
+    start = torch.randint(0, x.shape[-1] - band, (1,)).item()
+    return dict(freq_mask=(start, band))
+
+
 def _mixup_in_random_pool(x, cfg):  # MixupAugmenter mixes samples AND labels: it belongs to the supervised `fixed` pipeline
     raise NotImplementedError("mixup is a `fixed`-pipeline augmenter (supervised training); it is not drawn as a FOCAL view")
 
@@ -107,8 +131,9 @@ def draw_mixup(cfg, shapes):
 
 
 TIME_AUGMENTERS = {"no": None, "mixup": _mixup_in_random_pool, "negation": _negation, "scaling": _scaling, "horizontal_flip": _horizontal_flip,
-                   "permutation": _permutation, "time_warp": _time_warp, "mag_warp": _mag_warp}
-FREQ_AUGMENTERS = {"no": None, "phase_shift": _phase_shift}
+                   "permutation": _permutation, "time_warp": _time_warp, "mag_warp": _mag_warp, "jitter": _jitter,
+                   "channel_shuffle": _channel_shuffle, "time_mask": _time_mask}
+FREQ_AUGMENTERS = {"no": None, "phase_shift": _phase_shift, "freq_mask": _freq_mask}
 
 
 def _transform_all(items):
@@ -139,6 +164,44 @@ class Augmenter:
             if n not in FREQ_AUGMENTERS:
                 raise Exception(f"Invalid augmenter provided: {n}")
         self.aug_names = self.time_aug_names + self.freq_aug_names
+        self._derived = self._derive_extended(args.dataset_config)
+
+    def _derive_extended(self, cfg):
+        """Per-(location, modality) parameters of jitter / channel_shuffle / time_mask / freq_mask as the reference's classes derive them at
+        construction, for the ones the pool names; an impossible configuration is refused here, with the key to fix."""
+        out = {}
+        slots = [(loc, mod) for loc in self.locations for mod in self.modalities]
+        if "jitter" in self.aug_names:  # JitterAugmenter.init_value_range: value_range[mod] / 100 * std_in_percent
+            sec = cfg.get("jitter", {})
+            vr = sec.get("value_range")
+            if not isinstance(vr, dict) or any(mod not in vr for mod in self.modalities):
+                raise ValueError("jitter is in the augmenter pool but `jitter.value_range` does not give every modality's range: add "
+                                 "`value_range: {<modality>: <largest absolute time-domain sample>, ...}` for " + ", ".join(self.modalities)
+                                 + " to the dataset config's `jitter` section")
+            out["jitter"] = {k: {"std": float(vr[k[1]]) / 100 * sec["std_in_percent"]} for k in slots}
+        if "channel_shuffle" in self.aug_names:
+            ch = cfg.get("loc_mod_in_time_channels", {})
+            for loc, mod in slots:
+                c = ch.get(loc, {}).get(mod)
+                if c is not None and c > ops._lib.VIEW_MAX_CHANNELS:
+                    raise ValueError(f"channel_shuffle: `loc_mod_in_time_channels.{loc}.{mod}` = {c} exceeds the {ops._lib.VIEW_MAX_CHANNELS} "
+                                     "channels the shuffle is built for")
+            out["channel_shuffle"] = {k: {} for k in slots}
+        if "time_mask" in self.aug_names:  # TimeMaskAugmenter.py:17
+            d = floor(cfg["num_segments"] * cfg["time_mask"]["mask_ratio"])
+            if d < 1:
+                raise ValueError(f"time_mask: floor(num_segments * `time_mask.mask_ratio`) = {d}: the longest mask must be at least 1")
+            out["time_mask"] = {k: {"max_duration": d} for k in slots}
+        if "freq_mask" in self.aug_names:  # FreqMaskAugmenter.py:17-24: per modality, from the first location that has it
+            widths = {}
+            for loc, mod in slots:
+                if mod not in widths:
+                    widths[mod] = floor(cfg["loc_mod_spectrum_len"][loc][mod] * cfg["freq_mask"]["mask_ratio"])
+                    if widths[mod] <= 1:
+                        raise ValueError(f"freq_mask: floor(loc_mod_spectrum_len.{loc}.{mod} * `freq_mask.mask_ratio`) = {widths[mod]}: "
+                                         "the widest band must exceed 1 (the reference asserts it)")
+            out["freq_mask"] = {k: {"max_band_width": widths[k[1]]} for k in slots}
+        return out
 
     def to(self, device):
         return self
@@ -162,7 +225,12 @@ class Augmenter:
             out[loc] = {}
             for mod in self.modalities:
                 hit = fn is not None and random() < self.args.dataset_config[name]["prob"]
-                out[loc][mod] = fn(inputs[loc][mod], self.args.dataset_config.get(name, {})) if hit else {}
+                if hit:
+                    sec = self.args.dataset_config.get(name, {})
+                    extra = self._derived.get(name, {}).get((loc, mod))
+                    out[loc][mod] = fn(inputs[loc][mod], dict(sec, **extra) if extra else sec)
+                else:
+                    out[loc][mod] = {}
         return out
 
     def forward_fixed(self, time_loc_inputs, labels=None):
@@ -213,10 +281,11 @@ class Augmenter:
 
     # ------------------------------------------------------------------------------------------ random views, drawn on the device
     def device_draws_supported(self):
-        """The pool is made of augmenters focal_view_draw knows (every shipped `random_augmenters` pool is)."""
+        """The pool is made of augmenters focal_view_draw / focal_view_draw_ex know (every shipped `random_augmenters` pool is)."""
         cfg = self.args.dataset_config
         n_slots = sum(len(cfg["modality_names"]) for _ in cfg["location_names"])
-        return all(n in ops.VIEW_KINDS for n in self.aug_names) and 1 <= len(self.aug_names) <= 8 and n_slots <= ops._lib.VIEW_MAX_SLOTS
+        return (all(n in ops.VIEW_KINDS for n in self.aug_names) and 1 <= len(self.aug_names) <= ops._lib.VIEW_MAX_POOL_EX
+                and n_slots <= ops._lib.VIEW_MAX_SLOTS)
 
     def _device_state(self, inputs):
         flat = [(loc, mod) for loc in inputs for mod in inputs[loc]]
@@ -229,15 +298,22 @@ class Augmenter:
         if st is not None:
             return st
         cfg = self.args.dataset_config
+        dv, shape = self._derived, lambda k: inputs[k[0]][k[1]].shape
         pool = ops.view_pool([(n, cfg[n]["prob"] if n != "no" else 0.0) for n in self.aug_names],
                              [inputs[loc][mod].shape[2] for loc, mod in flat],
                              scaling_std=cfg.get("scaling", {}).get("std", 0.2),
                              mag_warp=(cfg.get("mag_warp", {}).get("magnitude", 0.05), cfg.get("mag_warp", {}).get("order", 4)),
-                             time_warp=(cfg.get("time_warp", {}).get("magnitude", 0.2), cfg.get("time_warp", {}).get("order", 6)))
+                             time_warp=(cfg.get("time_warp", {}).get("magnitude", 0.2), cfg.get("time_warp", {}).get("order", 6)),
+                             jitter_std=[dv["jitter"][k]["std"] for k in flat] if "jitter" in dv else None,
+                             channels=[shape(k)[1] for k in flat] if "channel_shuffle" in dv else None,
+                             time_mask=[(dv["time_mask"][k]["max_duration"], shape(k)[2]) for k in flat] if "time_mask" in dv else None,
+                             freq_mask=[(dv["freq_mask"][k]["max_band_width"], shape(k)[3]) for k in flat] if "freq_mask" in dv else None)
         dev = inputs[flat[0][0]][flat[0][1]].device
         n = len(flat)
         warps = any(k in ("mag_warp", "time_warp") for k in self.aug_names)
-        st = {"key": key, "flat": flat, "pool": pool, "plans": ops.new_view_plans(2, n, dev), "warps": warps,
+        # (an extended pool -- more than 8 entries, or jitter / channel_shuffle / time_mask / freq_mask -- draws an extra record beside each plan)
+        extras = ops.new_view_extras(2, n, dev) if isinstance(pool, ops._lib.ViewPoolEx) else None
+        st = {"key": key, "flat": flat, "pool": pool, "plans": ops.new_view_plans(2, n, dev), "extras": extras, "warps": warps,
               "both": {k: torch.empty((2 * inputs[k[0]][k[1]].shape[0], 2 * inputs[k[0]][k[1]].shape[1]) + tuple(inputs[k[0]][k[1]].shape[2:]),
                                       dtype=torch.float32, device=dev) for k in flat},
               # the warped copies and the tables of (view, slot): written only when the plan drew a warp
@@ -263,7 +339,10 @@ class Augmenter:
             stream_id = 0x56494557   # ("VIEW")
         # the draw's own state, started from one seed on every data-parallel rank: identical plans on all ranks (the reference draws once
         # per batch; the global batch is the batch), different dropout masks (runtime.rng_state stays per rank)
-        ops.view_draw_shared(st["pool"], 2, n, st["view_state"], stream_id, st["plans"])
+        if st["extras"] is None:
+            ops.view_draw_shared(st["pool"], 2, n, st["view_state"], stream_id, st["plans"])
+        else:
+            ops.view_draw_shared(st["pool"], 2, n, st["view_state"], stream_id, st["plans"], extras=st["extras"])
         if st["warps"]:
             ops.warp_plan_multi([dict(x=x[l][m], plan=st["plans"][v * n + i], tables=st["tables"][v][(l, m)], y=st["warped"][v][(l, m)])
                                  for v in range(2) for i, (l, m) in enumerate(flat)])
@@ -273,6 +352,8 @@ class Augmenter:
                 B = x[l][m].shape[0]
                 items.append(dict(x=x[l][m], plan=st["plans"][v * n + i], x_warped=st["warped"][v][(l, m)] if st["warps"] else x[l][m],
                                   out=st["both"][(l, m)][v * B:(v + 1) * B]))
+                if st["extras"] is not None:  # every rank draws the same jitter key: the rank salts the noise (independent per sample of the global batch)
+                    items[-1].update(extra=st["extras"][v * n + i], noise_salt=distributed.rank())
         outs = ops.fft_realpack_multi(items)
         views = ({loc: {} for loc in x}, {loc: {} for loc in x})
         for v in range(2):

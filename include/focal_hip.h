@@ -154,6 +154,76 @@ int focal_view_draw_shared(const focal_view_pool* pool, int n_views, int n_slots
 typedef struct { int rows, L; const float* x; const focal_view_plan* plan; float* tables; float* y; } focal_warp_problem;
 int focal_warp_plan_multi(int n, const focal_warp_problem* problems, const float* end_coef, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ jitter / channel shuffle / masks
+ * The four remaining view augmenters of the reference's data_augmenter package, as ADDITIONS beside the records above (no existing struct
+ * or export changes; the ABI number stays): a focal_view_extra travels beside a focal_view_plan / focal_aug_desc and is the identity
+ * when zeroed.
+ *   time domain   jitter           x' = x + N(0, 1) * std, i.i.d. per element                    JitterAugmenter.py:37-40
+ *                 channel shuffle  x'[:, c] = x[:, chan[c]]: one order for the whole batch        ChannelShuffleAugmenter.py:34-37
+ *                                  (packed spectrum: output pair (2c, 2c+1) = transform of source channel chan[c])
+ *                 time mask        x'[..., tmask_lo : tmask_lo + tmask_n] = 0, in every interval   TimeMaskAugmenter.py:37-41
+ *                                  (the reference draws interval-sized numbers and applies them to the SAMPLE axis; clipped at n)
+ *   freq domain   freq mask        bins [fmask_lo, fmask_lo + fmask_n) of all 2C channels = 0     FreqMaskAugmenter.py:44-48
+ * If several fields are set (the product sets one): mask_t(perm / flip / chan-select(scale * x) + noise), the DFT, the rotation, mask_f.
+ *
+ * The jitter noise is a pure function of (jitter_key, noise_salt, e), e = the flat index (mod 2^32) of the DESTINATION element in
+ * [B, C, I, n]; elements 2p and 2p + 1 share one Box-Muller pair.  With mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+ * x *= 0x846ca68b; x ^= x >> 16 (uint32 arithmetic):
+ *   k  = mix32(jitter_key ^ mix32(noise_salt * 0x9E3779B9 + 0x85EBCA6B))
+ *   u1 = 1 - (mix32(k + (2p) * 0x85EBCA6B) >> 8) / 2^24          in (0, 1]
+ *   u2 =     (mix32(k + (2p + 1) * 0x85EBCA6B) >> 8) / 2^24      in [0, 1)
+ *   z[2p] = sqrt(-2 ln u1) cos(2 pi u2),  z[2p + 1] = sqrt(-2 ln u1) sin(2 pi u2),  x'[e] += jitter_std * z[e]      (fp32)
+ * Under data parallelism every rank draws the same key (focal_view_draw_shared); noise_salt = the rank gives the samples of the global
+ * batch independent noise, as the reference's one torch.randn over the batch does. */
+#define FOCAL_VIEW_MAX_POOL_EX 16
+#define FOCAL_VIEW_MAX_CHANNELS 16
+enum { FOCAL_VIEW_JITTER = 8, FOCAL_VIEW_CHANNEL_SHUFFLE = 9, FOCAL_VIEW_TIME_MASK = 10, FOCAL_VIEW_FREQ_MASK = 11 };
+typedef struct {
+  float jitter_std;                       /* 0 = no noise */
+  uint32_t jitter_key;
+  int use_chan; int chan[FOCAL_VIEW_MAX_CHANNELS]; /* source channel of output channel c (a permutation of range(C)) */
+  int tmask_lo, tmask_n;                  /* samples [lo, lo + n) of every row zeroed before the DFT; n = 0: none */
+  int fmask_lo, fmask_n;                  /* bins [lo, lo + n) of every output row zeroed; n = 0: none */
+} focal_view_extra;
+/* focal_view_pool with room for the reference's full pool and the per-slot parameters of the four augmenters above */
+typedef struct {
+  int n_aug;
+  int kind[FOCAL_VIEW_MAX_POOL_EX]; float prob[FOCAL_VIEW_MAX_POOL_EX];
+  float scaling_std, mag_magnitude, time_magnitude;
+  int mag_order, time_order;
+  int intervals[FOCAL_VIEW_MAX_SLOTS];
+  float jitter_std[FOCAL_VIEW_MAX_SLOTS];  /* value_range[mod] / 100 * std_in_percent */
+  int channels[FOCAL_VIEW_MAX_SLOTS];      /* C of the slot's tensor, <= FOCAL_VIEW_MAX_CHANNELS */
+  int tmask_d[FOCAL_VIEW_MAX_SLOTS], tmask_i[FOCAL_VIEW_MAX_SLOTS]; /* D = floor(num_segments * mask_ratio); I = x.shape[2] */
+  int fmask_w[FOCAL_VIEW_MAX_SLOTS], fmask_n[FOCAL_VIEW_MAX_SLOTS]; /* W = floor(spectrum_len * mask_ratio); n = row length */
+} focal_view_pool_ex;
+/* focal_view_draw (advance = 0: `state` is the seed word, read only) / focal_view_draw_shared (advance = 1: `state` is the 4-word view
+ * state, moved on exactly as focal_view_draw_shared moves it) over an extended pool; extras: device [n_views][n_slots] beside plans.
+ * For a pool entry of an existing kind the plan bytes are those focal_view_draw writes from the same seed, stream id, view, slot,
+ * probabilities and pool position, and the extra is the identity.  The new kinds leave the plan's `aug` the identity and draw from
+ * indices of the (view, slot) key no existing kind uses (those use 0 .. 39):
+ *   jitter           jitter_key = raw draw 40, jitter_std = the slot's
+ *   time mask        duration = 1 + floor(u41 * D), start = floor(u42 * (I - duration))     (randint(1, D), torch.randint(0, I - duration))
+ *   freq mask        band = 1 + floor(u43 * W), start = floor(u44 * (n - band))
+ *   channel shuffle  Fisher-Yates over the slot's C channels, step i (C - 1 .. 1) from draw 48 + i
+ * Checked: pool of 1 .. 16; C <= 16; D >= 1 and I - D >= 1; W >= 2 and n - W >= 1 (for the slots in use, when the kind is pooled). */
+int focal_view_draw_ex(const focal_view_pool_ex* pool, int n_views, int n_slots, uint32_t* state, int advance, uint32_t stream_id,
+                       focal_view_plan* plans, focal_view_extra* extras, void* stream);
+/* focal_fft_realpack_multi with an extra per problem: extra_dev non-NULL = a DEVICE record read when the kernel runs (as `plan` is),
+ * else the host `extra` when has_extra, else none.  Host extras are checked (C <= 16 and chan a permutation of range(C) when use_chan;
+ * mask ranges inside [0, n]; std >= 0); a device record cannot be checked by the host, so the kernel clamps its values
+ * (channel entries to [0, C), mask ranges to [0, n], a negative std to 0) and IGNORES use_chan on a tensor of more than 16 channels: the
+ * table has no order for them.  focal_view_draw_ex never writes such a record (it refuses a pooled channel shuffle with C > 16); whoever
+ * writes records by hand for C > 16 gets jitter and the masks, not the shuffle.  A problem without an extra computes exactly
+ * what focal_fft_realpack_multi computes (one workgroup-uniform branch). */
+typedef struct { focal_fft_problem p; int has_extra; focal_view_extra extra; const focal_view_extra* extra_dev; uint32_t noise_salt; } focal_fft_problem_ex;
+int focal_fft_realpack_multi_ex(int n, const focal_fft_problem_ex* problems, void* stream);
+#ifdef __cplusplus
+static_assert(sizeof(focal_view_extra) == 92, "focal_view_extra");
+static_assert(sizeof(focal_view_pool_ex) == 4 + 2 * 64 + 20 + 7 * 32, "focal_view_pool_ex");
+static_assert(sizeof(focal_fft_problem_ex) == sizeof(focal_fft_problem) + 4 + 92 + 8 + 8, "focal_fft_problem_ex");
+#endif
+
 /* TimeWarp / MagWarp (data_augmenter/TimeWarpAugmenter.py:18,44, MagWarpAugmenter.py:18,44 -> tsai 0.3.7 TSTimeWarp / TSMagWarp;
  * SURVEY 8f rank 1): one smooth random curve per call over the flattened (I*S) axis of [B, C, I, S], shared by batch and channels;
  * x, y fp32 [rows = B*C][L = I*S].  Exactly one of the two table sets:
