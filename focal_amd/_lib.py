@@ -82,6 +82,10 @@ class EmbedDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "cin", "I", "S", "Hp", "Wp", "pw", "C0")] + [("eps", C.c_float)]
 
 
+class Embed2Desc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "cin", "I", "S", "Hp", "Wp", "pw", "C0", "stride")] + [("eps", C.c_float)]
+
+
 class LNDesc(C.Structure):
     _fields_ = [("dtype", C.c_int), ("rows", C.c_int), ("C", C.c_int), ("eps", C.c_float), ("gather", C.c_int),
                 ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int)]
@@ -170,6 +174,10 @@ PROTOTYPES = {
     "focal_mixup_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
     "focal_pad_patch_embed_ln_fwd": (C.c_int, [C.POINTER(EmbedDesc), P, P, P, P, P, P, P]),
     "focal_pad_patch_embed_ln2_fwd": (C.c_int, [C.POINTER(EmbedDesc), P, P, P, P, P, P, P, P, C.c_float, C.c_int, P, P, P]),
+    "focal_pad_patch_embed_ape_ln_fwd": (C.c_int, [C.POINTER(Embed2Desc), P, P, P, P, P, P, P, P]),
+    "focal_pad_patch_embed_ape_ln2_fwd": (C.c_int, [C.POINTER(Embed2Desc), P, P, P, P, P, P, P, P, P, C.c_float, C.c_int, P, P, P]),
+    "focal_ape_bwd": (C.c_int, [C.c_int, C.c_int, P, P, P]),
+    "focal_ape_add_fwd": (C.c_int, [C.c_int, C.c_int, P, P, P]),
     "focal_layernorm_fwd": (C.c_int, [C.POINTER(LNDesc), P, P, P, P, P, P]),
     "focal_layernorm_bwd": (C.c_int, [C.POINTER(LNDesc), P, P, P, P, P, C.c_int, P, P, P, C.POINTER(DropDesc), P]),
     "focal_mask_cast": (C.c_int, [C.c_int, C.c_int, C.c_int, P, C.POINTER(DropDesc), P, P]),

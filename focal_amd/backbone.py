@@ -36,11 +36,33 @@ def is_hot_supervised(name):
     return not name.startswith(SUPERVISED_DEAD)
 
 
+APE_PREFIX = "absolute_pos_embed."
+
+
+def is_hot_ape(name):
+    """FOCAL pretraining with `APE: true`: the absolute position embedding is added to the tokens and trains (the reference's
+    freeze_patch_embedding matches "patch_embed" only, general_utils/weight_utils.py:85-94), so it joins the arena."""
+    return is_hot(name) or name.startswith(APE_PREFIX)
+
+
+def is_hot_supervised_ape(name):
+    """Supervised training from scratch with `APE: true`."""
+    return is_hot_supervised(name) or name.startswith(APE_PREFIX)
+
+
 class HipBackbone(nn.Module):
     def _init_hip(self, args):
         self.compute_dtype = runtime.compute_dtype_from(args)
         self.supervised = getattr(args, "train_mode", "") == "supervised"
-        self._hot = is_hot_supervised if self.supervised else (is_hot_with_head if getattr(args, "stage", "pretrain") == "finetune" else is_hot)
+        # (with APE off -- every shipped config -- the rule, and with it the arena's layout, is what it was; the finetune stage keeps the
+        # position embedding out of the arena: it is a frozen operand there, read where it lives)
+        ape = bool((getattr(self, "config", None) or {}).get("APE", False))
+        if self.supervised:
+            self._hot = is_hot_supervised_ape if ape else is_hot_supervised
+        elif getattr(args, "stage", "pretrain") == "finetune":
+            self._hot = is_hot_with_head
+        else:
+            self._hot = is_hot_ape if ape else is_hot
         self._arena = None
         self._named = None
         self._fwd_calls = 0
@@ -93,7 +115,8 @@ class HipBackbone(nn.Module):
         for m in stage_of.values():
             if m:
                 last[m.group(1)] = max(last.get(m.group(1), 0), int(m.group(2)))
-        return [n for n, m in stage_of.items() if m is None or int(m.group(2)) == last[m.group(1)]]
+        # (the position embedding's gradient is the LAST thing an encoder's backward pass writes: never final after the first phase)
+        return [n for n, m in stage_of.items() if not n.startswith(APE_PREFIX) and (m is None or int(m.group(2)) == last[m.group(1)])]
 
     def rng_state(self):
         return runtime.rng_state(next(self.parameters()).device)

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import (ACT_GELU, ACT_NONE, ACT_RELU_OUT, EPI_GELU, EPI_NONE, EPI_RELU, EPI_RESIDUAL, FOCAL_BF16, FOCAL_F32,
-                   AdamWDesc, AttnDesc, BNDesc, ConvDesc, ConvInDesc, DropDesc, EmbedDesc, FFTDesc, GRUDesc, LinearDesc,
+                   AdamWDesc, AttnDesc, BNDesc, ConvDesc, ConvInDesc, DropDesc, Embed2Desc, EmbedDesc, FFTDesc, GRUDesc, LinearDesc,
                    LNDesc, LossDesc, MlpDesc, check)
 
 _TORCH2CODE = {torch.float32: FOCAL_F32, torch.bfloat16: FOCAL_BF16}
@@ -476,6 +476,42 @@ def pad_patch_embed_ln(x, w, b, gamma, beta, Hp, Wp, pw, eps=1e-5, next_ln=None)
     check(_lib.load().focal_pad_patch_embed_ln2_fwd(C.byref(d), _p(x), _p(w), _p(b), _p(gamma), _p(beta), _p(out), _p(g2), _p(b2),
                                                     1e-5, code(dt), _p(y_ln), _p(stats), _stream()))
     return out, y_ln, stats
+
+
+def pad_patch_embed_ape_ln(x, w, b, gamma, beta, Hp, Wp, pw, stride=1, ape=None, eps=1e-5, next_ln=None):
+    """pad_patch_embed_ln on the RAW input [B, cin, I, S] with the reference's in_stride folded into the patch gather (w is
+    [C0, cin * stride, 1, pw]) and the absolute position embedding `ape` ([Hp * Wp, C0] values, or None) added to the tokens;
+    with next_ln the second LayerNorm reads the position-embedded tokens."""
+    _need_cuda(x, w, b, gamma, beta, ape)
+    B, cin, I, S = x.shape
+    C0 = w.shape[0]
+    if ape is not None and ape.numel() != Hp * Wp * C0:
+        raise _lib.FocalHipError(f"absolute position embedding of {ape.numel()} values on a {Hp} x {Wp} x {C0} token grid")
+    out = torch.empty(B * Hp * Wp, C0, dtype=torch.float32, device=x.device)
+    d = Embed2Desc(B, cin, I, S, Hp, Wp, pw, C0, stride, eps)
+    if next_ln is None:
+        check(_lib.load().focal_pad_patch_embed_ape_ln_fwd(C.byref(d), _p(x), _p(w), _p(b), _p(gamma), _p(beta), _p(ape), _p(out), _stream()))
+        return out
+    g2, b2, dt = next_ln
+    y_ln = torch.empty(B * Hp * Wp, C0, dtype=dt, device=x.device)
+    stats = torch.empty(B * Hp * Wp, 2, dtype=torch.float32, device=x.device)
+    check(_lib.load().focal_pad_patch_embed_ape_ln2_fwd(C.byref(d), _p(x), _p(w), _p(b), _p(gamma), _p(beta), _p(ape), _p(out), _p(g2), _p(b2),
+                                                        1e-5, code(dt), _p(y_ln), _p(stats), _stream()))
+    return out, y_ln, stats
+
+
+def ape_add(x, ape):
+    """x (fp32 [N * HW, C0]) += ape (HW * C0 values) per sample, in place."""
+    _need_cuda(x, ape)
+    cols = ape.numel()
+    check(_lib.load().focal_ape_add_fwd(x.numel() // cols, cols, _p(x), _p(ape), _stream()))
+
+
+def ape_bwd(g, dape):
+    """dape (fp32, HW * C0 values) += the sum over the N samples of g (fp32 [N * HW, C0]): the absolute position embedding's gradient."""
+    _need_cuda(g, dape)
+    cols = dape.numel()
+    check(_lib.load().focal_ape_bwd(g.numel() // cols, cols, _p(g), _p(dape), _stream()))
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm

@@ -6,7 +6,8 @@ The classifier path (`class_head=True`: TransformerFusionBlock over the modality
 the finetune stage (frozen encoders, head trained) and for supervised training from scratch (gradient flows on into the encoders and
 the patch embedding).  On a multi-location dataset the FOCAL pretraining path runs the reference's location fusion (:126-150,
 :226-242: per modality, loc_context_layers + loc_fusion_layer over the L location features) as one HIP stage per modality
-(focal_amd/loc_engine.py); the classifier path on such a dataset raises.
+(focal_amd/loc_engine.py); the classifier path on such a dataset raises.  The section's `APE` and `in_stride` switches (reference
+:184-208, :222-224) run inside the patch-embedding kernel (focal_amd/swin_engine.py, csrc/embed.hip) on every one of these paths.
 """
 import os
 import sys
@@ -71,9 +72,10 @@ class SW_Transformer(HipBackbone):
             self.geometry[loc] = {}
             for mod in self.modalities:
                 stride = cfg["in_stride"][mod]
-                if stride != 1:
-                    raise NotImplementedError("in_stride != 1 is not used by any shipped config")
                 spectrum = dcfg["loc_mod_spectrum_len"][loc][mod]
+                if stride < 1 or spectrum % stride != 0:
+                    # (the reference's reshape [b, i, s, c] -> [b, i, s // stride, c * stride] fails on such a spectrum at the first batch)
+                    raise ValueError(f"SW_Transformer.in_stride[{mod}] = {stride} does not divide loc_mod_spectrum_len[{loc}][{mod}] = {spectrum}")
                 window, patch = list(cfg["window_size"][mod]), list(cfg["patch_size"]["freq"][mod])
                 depths = list(cfg["time_freq_block_num"][mod])
                 padded = get_padded_size((self.num_segments, spectrum // stride), window, patch, len(depths))
@@ -100,8 +102,8 @@ class SW_Transformer(HipBackbone):
                 last = stages[-1]
                 self.mod_in_layers[loc][mod] = nn.Linear(last["H"] * last["W"] * last["C"], cfg["loc_out_channels"])
                 self.geometry[loc][mod] = dict(grid=grid, patch=patch, window=window, stages=stages,
-                                               heads=cfg["time_freq_head_num"], pad_img=padded)
-                if spectrum // patch[1] > grid[1] or self.num_segments > grid[0]:
+                                               heads=cfg["time_freq_head_num"], pad_img=padded, stride=stride)
+                if (spectrum // stride) // patch[1] > grid[1] or self.num_segments > grid[0]:
                     raise ValueError("padded patch grid smaller than the input")
         if len(self.locations) > 1:
             # location fusion, as the reference builds it: per modality loc_block_num encoder layers + one attention fusion block
@@ -200,7 +202,7 @@ class SW_Transformer(HipBackbone):
         """`backbone(freq_x, class_head=True)` -> logits (reference: models/SW_Transformer.py:269-276).  This is the finetuning path: the encoders in front run
         forward-only (finetuning freezes them, general_utils/weight_utils.py:61-80), the head -- modality fusion + class layer -- is one
         differentiable node (focal_amd/head_engine.py)."""
-        if self._hot.__name__ == "is_hot":
+        if self._hot.__name__ in ("is_hot", "is_hot_ape"):
             raise NotImplementedError("class_head=True needs the classifier head in the parameter arena: build the model with "
                                       "args.stage = 'finetune' (or supervised train_mode)")
         if self.supervised:  # supervised training from scratch (train_utils/supervised_train.py): the gradient flows on into the encoders

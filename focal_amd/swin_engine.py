@@ -138,18 +138,42 @@ class SwinModEncoder:
         pre_ln = None  # (a1, st1) of the next block when the kernel before it already produced them
         first = f"{self.pre}.0.blocks.0"
         embed_saved = None
+        # The reference's two input switches (models/SW_Transformer.py:184-208, :222-224).  in_stride folds `stride` neighbouring spectrum
+        # bins into channels; APE adds a learned [Hp * Wp, C0] table to the embedded tokens.  The table trains in FOCAL pretraining and in
+        # supervised training (it lives in the arena then) and is a frozen operand of the finetune stage (read where it lives).
+        stride = geo.get("stride", 1)
+        ape = ape_name = None
+        if bb.config["APE"]:
+            ape_name = f"absolute_pos_embed.{self.loc}.{self.mod}"
+            ape = ar.master(ape_name) if ape_name in ar.index else P(ape_name)
         if getattr(bb, "supervised", False):
             # Supervised training from scratch trains the patch embedding too (it is frozen only in FOCAL pretraining): the strided
             # Conv2d runs on the patchifying convolution kernels that already have a weight gradient (focal_conv_in_*: DeepSense's first
             # layer is the same operator), on the zero-padded spectrum; its LayerNorm on the LayerNorm kernels.  The fused
             # pad + embed + LayerNorm kernel of the pretraining path has no backward.
             Hp, Wp, pw = geo["grid"][0], geo["grid"][1], geo["patch"][1]
+            if stride != 1:  # [b, c, i, s] -> [b, c * stride, i, s / stride] as the reference folds it: data movement only
+                b_, c_, i_, s_ = x_freq.shape
+                # (contiguous: F.pad below would keep the permuted view's channels-last strides, and the kernels read NCHW)
+                x_freq = x_freq.permute(0, 2, 3, 1).reshape(b_, i_, s_ // stride, c_ * stride).permute(0, 3, 1, 2).contiguous()
             _, cin, I, S = x_freq.shape
             xpad = torch.nn.functional.pad(x_freq, (0, Wp * pw - S, 0, Hp - I))  # data movement only
             d_pe = ops.conv_in_desc(B, cin, Hp, Wp * pw, Wp, pw, pw, 0, geo["stages"][0]["C"])
             z = ops.conv_in_fwd(d_pe, xpad, ar.master(f"{pe}.proj.weight"), ar.master(f"{pe}.proj.bias"))
             x, st_e = ops.layernorm_fwd(z, ar.master(f"{pe}.norm.weight"), ar.master(f"{pe}.norm.bias"), torch.float32)
+            if ape is not None:  # (one more pass over the tokens, in place, as this path's stand-alone LayerNorm before it is)
+                ops.ape_add(x, ape)
             embed_saved = dict(d=d_pe, xpad=xpad, z=z, st=st_e)
+        elif stride != 1 or ape is not None:
+            ape2 = None if ape is None else ape.view(-1, ape.shape[-1])
+            emb = (x_freq, P(f"{pe}.proj.weight"), P(f"{pe}.proj.bias"), P(f"{pe}.norm.weight"), P(f"{pe}.norm.bias"),
+                   geo["grid"][0], geo["grid"][1], geo["patch"][1])
+            if geo["stages"][0]["C"] == 64:  # (as below: the kernel also emits block 0's norm1, of the position-embedded tokens)
+                x, a1_0, st1_0 = ops.pad_patch_embed_ape_ln(*emb, stride=stride, ape=ape2, next_ln=(
+                    ar.master(f"{first}.norm1.weight"), ar.master(f"{first}.norm1.bias"), ct))
+                pre_ln = (a1_0, st1_0)
+            else:
+                x = ops.pad_patch_embed_ape_ln(*emb, stride=stride, ape=ape2)
         elif geo["stages"][0]["C"] == 64:  # the embedding kernel also emits block 0's norm1
             x, a1_0, st1_0 = ops.pad_patch_embed_ln(x_freq, P(f"{pe}.proj.weight"), P(f"{pe}.proj.bias"), P(f"{pe}.norm.weight"),
                                                     P(f"{pe}.norm.bias"), geo["grid"][0], geo["grid"][1], geo["patch"][1],
@@ -158,11 +182,11 @@ class SwinModEncoder:
         else:
             x = ops.pad_patch_embed_ln(x_freq, P(f"{pe}.proj.weight"), P(f"{pe}.proj.bias"), P(f"{pe}.norm.weight"),
                                        P(f"{pe}.norm.bias"), geo["grid"][0], geo["grid"][1], geo["patch"][1])
-        if bb.config["APE"]:
-            raise ops._lib.FocalHipError("absolute position embedding (APE: True) is outside the HIP hot path")
         p_drop = bb.drop_rate if training else 0.0
         p_attn = bb.attn_drop_rate if training else 0.0
-        saved = {"B": B, "view": view, "training": training, "blocks": [], "merges": [], "embed": embed_saved}
+        saved = {"B": B, "view": view, "training": training, "blocks": [], "merges": [], "embed": embed_saved,
+                 # the table's gradient is wanted where it trains: block 0 then hands the residual-stream gradient on (_backward_blocks)
+                 "ape": ape_name if (ape_name is not None and ape_name in ar.index) else None}
         uid = 0
         for si, st in enumerate(geo["stages"]):
             H, W, Cc = st["H"], st["W"], st["C"]
@@ -446,7 +470,8 @@ class SwinModEncoder:
             if plan.ln1_bwd == "dx":  # dX of qkv and norm1's backward in one kernel
                 # the encoder's first block behind the frozen patch embedding: its input is a leaf nobody differentiates, so the
                 # residual-stream gradient stops here -- only norm1's dgamma / dbeta are produced (no read / update / re-cast of g)
-                g_out = None if (k == 0 and saved.get("embed") is None and not want_gm) else g
+                # (with a trained position embedding in front it goes on: the table's gradient is its sum over the samples)
+                g_out = None if (k == 0 and saved.get("embed") is None and saved.get("ape") is None and not want_gm) else g
                 ops.linear_bwd_data_ln(s["d_qkv"], dqkv, ar.operand(f"{pb}.attn.qkv.weight"), s["x"], s["st1"], ar.master(f"{pb}.norm1.weight"), g_out,
                                        ar.g(f"{pb}.norm1.weight"), ar.g(f"{pb}.norm1.bias"), g_masked=gm if want_gm else None, mask=nxt)
             else:
@@ -467,6 +492,8 @@ class SwinModEncoder:
         ct = bb.compute_dtype
         g = state["g"]
         # g now holds dL/d(patch-embed tokens).  FOCAL pretraining: the embedding is frozen and its input is a leaf -> stop here.
+        if saved.get("ape") is not None:  # x = LN(embed) + ape: d ape = the sum of g over the pass's samples (both views in one pass: 2B)
+            ops.ape_bwd(g, ar.g(saved["ape"]))
         es = saved.get("embed")
         if es is not None:  # supervised training: LayerNorm backward, then the convolution's weight / bias gradient
             pe = f"patch_embed.{self.loc}.{self.mod}"

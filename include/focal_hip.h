@@ -251,6 +251,24 @@ int focal_pad_patch_embed_ln_fwd(const focal_embed_desc* d, const float* x, cons
 int focal_pad_patch_embed_ln2_fwd(const focal_embed_desc* d, const float* x, const float* w, const float* b,
                                   const float* gamma, const float* beta, float* tokens, const float* gamma2, const float* beta2,
                                   float eps2, int ln_dtype, void* y_ln, float* stats, void* stream);
+/* The same two with the reference's `in_stride` and `APE` switches (SW_Transformer.py:184-208, :222-224).  cin and S describe the RAW
+ * input [B, cin, I, S]; the kernel folds `stride` neighbouring spectrum bins into channels inside its patch gather (embedded channel
+ * (s % stride) * cin + c at position s / stride; S % stride == 0), so w is [C0, cin * stride, 1, pw] and Wp * pw >= S / stride.
+ * ape: NULL, or fp32 [Hp*Wp, C0] added to the LayerNorm output by the token's position inside its sample: tokens = LN(embed) + ape, and
+ * in the ln2 form y_ln / stats are those of the position-embedded tokens.  stride == 1 with ape == NULL issues the launch of the entry
+ * points above.  x, w, b, gamma, beta, ape, tokens, gamma2, beta2, y_ln, stats: 16-byte aligned. */
+typedef struct { int B, cin, I, S, Hp, Wp, pw, C0, stride; float eps; } focal_embed2_desc;
+int focal_pad_patch_embed_ape_ln_fwd(const focal_embed2_desc* d, const float* x, const float* w, const float* b,
+                                     const float* gamma, const float* beta, const float* ape, float* tokens, void* stream);
+int focal_pad_patch_embed_ape_ln2_fwd(const focal_embed2_desc* d, const float* x, const float* w, const float* b,
+                                      const float* gamma, const float* beta, const float* ape, float* tokens, const float* gamma2,
+                                      const float* beta2, float eps2, int ln_dtype, void* y_ln, float* stats, void* stream);
+/* Gradient of the absolute position embedding: dape[j] += sum_n g[n][j], g fp32 [N, cols] the residual-stream gradient at block 0's
+ * input (N samples of the pass, cols = Hp*Wp*C0, cols % 4 == 0, both pointers 16-byte aligned).  Accumulates (fp32 atomics when the
+ * samples are split over workgroups). */
+int focal_ape_bwd(int N, int cols, const float* g, float* dape, void* stream);
+/* The add alone, in place, for a caller that embeds with other kernels (the supervised path): x[n][j] += ape[j], x fp32 [N, cols]. */
+int focal_ape_add_fwd(int N, int cols, float* x, const float* ape, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ LayerNorm
  * nn.LayerNorm(eps 1e-5) of models/SwinModules.py:253,258,376.  x fp32 [rows, C]; y `dtype`; stats fp32
