@@ -464,7 +464,8 @@ __global__ void permute_unpack_add_kernel(const float* __restrict__ src, float* 
     dst[e] += src[((long)a * Cd + c) * Bd + b];
   }
 }
-// w_bwd[ci][t'][co] = w[co][ci][k-1-t']: the data gradient of a "same" conv is the conv with flipped taps
+// w_bwd[ci][t'][co] = w[co][ci][k-1-t']: the data gradient of a "same" conv is the conv with flipped taps (and, for an even k, with the
+// pads exchanged: conv_pad_bwd below)
 template <typename TD> __global__ void conv_pack_bwd_kernel(const float* __restrict__ w, TD* __restrict__ dst, int Co, int Ci, int k) {
   const long n = (long)Co * Ci * k;
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
@@ -576,7 +577,7 @@ extern "C" int focal_unpack_add_multi(int n, const focal_pack_entry* entries, vo
 static int conv_check(const focal_conv_desc* d) {
   FOCAL_CHECK_ARG(d != nullptr, "conv: null descriptor");
   FOCAL_CHECK_ARG(d->dtype == FOCAL_F32 || d->dtype == FOCAL_BF16, "conv: bad dtype");
-  FOCAL_CHECK_ARG(d->k % 2 == 1 && d->k >= 1, "conv: kernel length %d must be odd ('same' padding)", d->k);
+  FOCAL_CHECK_ARG(d->k >= 1, "conv: kernel length %d must be at least 1", d->k);
   FOCAL_CHECK_ARG(d->rows % d->S == 0 && d->C_in % 8 == 0 && d->C_out % 8 == 0, "conv: rows %% S != 0 or channels not multiples of 8");
   return FOCAL_OK;
 }
@@ -587,6 +588,17 @@ static MaskParams conv_window(int S, int C, int pad) {
   return m;
 }
 static size_t esize(int dtype) { return dtype == FOCAL_F32 ? 4 : 2; }
+// 'same' padding of a length-k filter: k - 1 zeros in all, (k - 1) / 2 of them on the left (an even k carries the extra one on the right).
+// The forward convolution, its statistics form and the weight gradient read token m + t - conv_pad_fwd(k) at tap t; the data gradient
+// correlates dz with the FLIPPED taps (focal_conv_pack_bwd), whose left pad is what the forward had on the right.  Equal for odd k.
+static int conv_pad_fwd(int k) { return (k - 1) / 2; }
+static int conv_pad_bwd(int k) { return k - 1 - conv_pad_fwd(k); }
+static const char* conv_ring_name(int k, int epi) {  // (k = 3 .. 5 only: every caller sits behind conv_ring_fits)
+  static const char* const names[3][3] = {{"conv_ring_kernel<3, store>", "conv_ring_kernel<3, stats>", "conv_ring_kernel<3, resid>"},
+                                          {"conv_ring_kernel<4, store>", "conv_ring_kernel<4, stats>", "conv_ring_kernel<4, resid>"},
+                                          {"conv_ring_kernel<5, store>", "conv_ring_kernel<5, stats>", "conv_ring_kernel<5, resid>"}};
+  return k >= 3 && k <= 5 ? names[k - 3][epi] : "conv_ring_kernel<?>";
+}
 
 // focal_conv_fwd + the training-mode statistics of the BatchNorm behind it (focal_bn_stats, FOCAL_BN_TRAIN) from the GEMM's epilogue: the
 // pre-BN tensor z is not read back for them and the statistics launch is gone (EPI_STORE_STATS, gemm_body.inc).
@@ -601,7 +613,7 @@ extern "C" int focal_conv_fwd_bn(const focal_conv_desc* d, const void* x, const 
     focal_set_error("conv_fwd_bn: bf16 operands only (fp32: focal_conv_fwd + focal_bn_stats)");
     return FOCAL_EUNSUPPORTED;
   }
-  const int pad = d->k / 2, K = d->k * d->C_in;
+  const int pad = conv_pad_fwd(d->k), K = d->k * d->C_in;
   {
     const int G = bn->groups > 1 ? bn->groups : 1;
     if (conv_ring_fits(d, d->C_in, d->C_out, x, w_fwd, G) && (G == 1 || bn->stat_rows <= 0)) {
@@ -611,7 +623,7 @@ extern "C" int focal_conv_fwd_bn(const focal_conv_desc* d, const void* x, const 
       rp.bn_sums = scratch; rp.bn_mean_rstd = mean_rstd; rp.bn_run_mean = running_mean; rp.bn_run_var = running_var;
       rp.bn_rows = G > 1 ? bn->rows / G : (bn->stat_rows > 0 ? bn->stat_rows : bn->rows);
       rp.bn_eps = bn->eps; rp.bn_momentum = bn->momentum; rp.bn_groups = G;
-      focal_note_kernel(d->k == 5 ? "conv_ring_kernel<5, stats>" : "conv_ring_kernel<3, stats>");
+      focal_note_kernel(conv_ring_name(d->k, CR_STORE_STATS));
       hipError_t e = conv_ring_launch<CR_STORE_STATS>(rp, d->k, G, (hipStream_t)stream);
       if (e != hipSuccess) { focal_set_error("conv_fwd_bn (row ring): launch failed: %s", hipGetErrorString(e)); return FOCAL_EHIP; }
       return FOCAL_OK;
@@ -642,7 +654,7 @@ extern "C" int focal_conv_fwd_bn(const focal_conv_desc* d, const void* x, const 
 
 // 1: focal_conv_fwd_bn takes mean_rstd = NULL for this convolution (the row-ring kernel runs it) and focal_bn_act_fwd_sums finishes the statistics
 extern "C" int focal_conv_fwd_bn_sums_supported(const focal_conv_desc* d, const focal_bn_desc* bn, const void* x, const void* w_fwd) {
-  if (d == nullptr || bn == nullptr || d->k % 2 != 1 || d->S <= 0 || d->rows % d->S != 0) return 0;
+  if (d == nullptr || bn == nullptr || d->k < 1 || d->S <= 0 || d->rows % d->S != 0) return 0;
   const char* sel = getenv("FOCAL_CONV_BN_SUMS");
   if (sel != nullptr && sel[0] == '0') return 0;
   const int G = bn->groups > 1 ? bn->groups : 1;
@@ -652,12 +664,12 @@ extern "C" int focal_conv_fwd_bn_sums_supported(const focal_conv_desc* d, const 
 extern "C" int focal_conv_fwd(const focal_conv_desc* d, const void* x, const void* w_fwd, const float* bias, float* z, void* stream) {
   if (int rc = conv_check(d)) return rc;
   FOCAL_CHECK_ARG(x && w_fwd && z, "conv_fwd: null tensor");
-  const int pad = d->k / 2, K = d->k * d->C_in;
+  const int pad = conv_pad_fwd(d->k), K = d->k * d->C_in;
   if (conv_ring_fits(d, d->C_in, d->C_out, x, w_fwd, 1)) {
     ConvRingParams rp;
     memset(&rp, 0, sizeof(rp));
     rp.x = (const bf16_t*)x; rp.w = (const bf16_t*)w_fwd; rp.bias = bias; rp.out = z; rp.rows = d->rows; rp.S = d->S;
-    focal_note_kernel(d->k == 5 ? "conv_ring_kernel<5, store>" : "conv_ring_kernel<3, store>");
+    focal_note_kernel(conv_ring_name(d->k, CR_STORE));
     hipError_t e = conv_ring_launch<CR_STORE>(rp, d->k, 1, (hipStream_t)stream);
     if (e != hipSuccess) { focal_set_error("conv_fwd (row ring): launch failed: %s", hipGetErrorString(e)); return FOCAL_EHIP; }
     return FOCAL_OK;
@@ -678,12 +690,12 @@ extern "C" int focal_conv_bwd_data(const focal_conv_desc* d, const void* dz, con
                                    void* stream) {
   if (int rc = conv_check(d)) return rc;
   FOCAL_CHECK_ARG(dz && w_bwd && g_in && g_out, "conv_bwd_data: null tensor");
-  const int pad = d->k / 2, K = d->k * d->C_out;
+  const int pad = conv_pad_bwd(d->k), K = d->k * d->C_out;
   if (conv_ring_fits(d, d->C_out, d->C_in, dz, w_bwd, 1) && ((uintptr_t)g_in % 16 == 0) && ((uintptr_t)g_out % 16 == 0)) {
     ConvRingParams rp;
     memset(&rp, 0, sizeof(rp));
     rp.x = (const bf16_t*)dz; rp.w = (const bf16_t*)w_bwd; rp.resid = g_in; rp.out = g_out; rp.rows = d->rows; rp.S = d->S;
-    focal_note_kernel(d->k == 5 ? "conv_ring_kernel<5, resid>" : "conv_ring_kernel<3, resid>");
+    focal_note_kernel(conv_ring_name(d->k, CR_RESID));
     hipError_t e = conv_ring_launch<CR_RESID>(rp, d->k, 1, (hipStream_t)stream);
     if (e != hipSuccess) { focal_set_error("conv_bwd_data (row ring): launch failed: %s", hipGetErrorString(e)); return FOCAL_EHIP; }
     return FOCAL_OK;
@@ -705,7 +717,7 @@ extern "C" int focal_conv_bwd_weight(const focal_conv_desc* d, const void* dz, c
                                      void* stream) {
   if (int rc = conv_check(d)) return rc;
   FOCAL_CHECK_ARG(dz && x && dw_packed, "conv_bwd_weight: null tensor");
-  const int pad = d->k / 2, K = d->k * d->C_in;
+  const int pad = conv_pad_fwd(d->k), K = d->k * d->C_in;
   GemmSpec s{d->dtype, d->dtype, d->dtype, FOCAL_F32, true, true, PRO_NONE, PRO_CONV, EPI_ATOMIC};
   GemmParams p;
   memset(&p, 0, sizeof(p));

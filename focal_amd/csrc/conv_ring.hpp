@@ -3,6 +3,9 @@
 //
 //   out[m][n] = sum_t sum_c x[m + t - pad][c] * w[n][t * 64 + c]   (+ bias[n] | + resid[m][n]),   taps leaving m's interval of S tokens are zero
 //
+// k = 3, 4, 5.  pad = (k - 1) / 2 in the forward forms; the data-gradient form runs the flipped taps with pad = k / 2 (an even 'same' filter
+// carries its extra zero on the right, so its transpose carries it on the left).
+//
 // Why not the GEMM with a window prologue (gemm.hpp PRO_CONV, the round-1 tile kernel): that kernel re-forms the k-fold overlapping operand
 // element by element (a validity test per element and tap) and re-stages the 40 KB weight per 64-row tile; it ran the k = 5 layer of the
 // step (102 400 rows: 13 MB in, 26 MB out) in 19.4 us forward, 27.5 us with the BatchNorm statistics, 24.7 us as the data gradient
@@ -37,7 +40,10 @@ struct ConvRingParams {
 
 template <int KT, int EPI>
 __global__ __launch_bounds__(320, 3) void conv_ring_kernel(const ConvRingParams p) {
-  constexpr int BM = 64, HALO = 8, TROWS = BM + 2 * HALO, BUF = TROWS * 128, NBUF = 3, PIECES = TROWS / 8, PAD = KT / 2, K = KT * 64, KS = KT * 2;
+  constexpr int BM = 64, HALO = 8, TROWS = BM + 2 * HALO, BUF = TROWS * 128, NBUF = 3, PIECES = TROWS / 8, K = KT * 64, KS = KT * 2;
+  // the left pad of a 'same' filter: (KT - 1) / 2 forward; the data gradient (flipped taps) has the forward's right pad, KT / 2, on its left.
+  // The same number for odd KT.  (HALO covers a pad of up to 8 rows either side.)
+  constexpr int PAD = EPI == CR_RESID ? KT / 2 : (KT - 1) / 2;
   extern __shared__ __attribute__((aligned(1024))) char cr_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -265,7 +271,7 @@ __global__ __launch_bounds__(320, 3) void conv_ring_kernel(const ConvRingParams 
   }
 }
 
-// Does the row-ring kernel take this convolution?  64 -> 64 channels, k = 3 / 5, bf16 operands, whole 64-row tiles (per statistics group),
+// Does the row-ring kernel take this convolution?  64 -> 64 channels, k = 3 / 4 / 5, bf16 operands, whole 64-row tiles (per statistics group),
 // intervals of at least k tokens, 16-byte aligned operands.  FOCAL_CONV_RING=0 keeps the sliding-window GEMM (A/B runs, the tests' second path).
 // Alone on the chip the kernel is 5 - 25 % faster than that GEMM per launch (k = 5 / 3 forward 16.3 / 12.1 vs ~20 / ~14 us, data gradient
 // 21.2 / 18.9 vs ~24 / ~21; tools/prof_conv.sh); inside the replayed DeepSense step +1.4 ... +2.3 %, +2.0 ... +2.9 % with the sums-only
@@ -273,7 +279,7 @@ __global__ __launch_bounds__(320, 3) void conv_ring_kernel(const ConvRingParams 
 // fragment set spilled: that one LOST 2 - 4 % in the step).
 static inline bool conv_ring_fits(const focal_conv_desc* d, int c_in, int c_out, const void* x, const void* w, int groups) {
   const char* sel = getenv("FOCAL_CONV_RING");  // (read per call: the tests switch paths inside one process)
-  if ((sel != nullptr && sel[0] == '0') || d->dtype != FOCAL_BF16 || c_in != 64 || c_out != 64 || (d->k != 3 && d->k != 5)) return false;
+  if ((sel != nullptr && sel[0] == '0') || d->dtype != FOCAL_BF16 || c_in != 64 || c_out != 64 || d->k < 3 || d->k > 5) return false;
   if (groups < 1 || d->rows % (64 * groups) != 0 || d->rows >= (1 << 20) || d->S < d->k || d->S >= (1 << 12)) return false;
   return ((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0);
 }
@@ -295,6 +301,7 @@ static inline hipError_t conv_ring_launch(ConvRingParams& p, int k, int groups, 
   p.s_magic = 0xFFFFFFFFu / (uint32_t)p.S + 1u;
   const int wgs = p.wgs_per_group * groups;
   if (k == 5) FOCAL_LAUNCH((conv_ring_kernel<5, EPI>), dim3(wgs), dim3(320), LDS_BYTES, stream, p);
+  else if (k == 4) FOCAL_LAUNCH((conv_ring_kernel<4, EPI>), dim3(wgs), dim3(320), LDS_BYTES, stream, p);
   else FOCAL_LAUNCH((conv_ring_kernel<3, EPI>), dim3(wgs), dim3(320), LDS_BYTES, stream, p);
   return hipGetLastError();
 }

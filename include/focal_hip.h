@@ -492,7 +492,8 @@ typedef struct { int B, cin, I, S_in, S_out, k, stride, pad_left, C; } focal_con
 int focal_conv_in_fwd(const focal_conv_in_desc* d, const float* x, const float* w, const float* bias, float* z, void* stream);
 int focal_conv_in_bwd_weight(const focal_conv_in_desc* d, const float* x, const void* dz, int dz_dtype, float* dw, float* dbias,
                              void* stream);
-/* [1,k] "same" convs (k odd) = MFMA GEMMs over a sliding token window.  Operand orders: w_fwd [C_out][k][C_in],
+/* [1,k] "same" convs (any k >= 1; k - 1 zeros in all, (k - 1) / 2 on the left and the rest on the right, as torch pads an even filter;
+ * the data gradient runs the flipped taps with k / 2 on the left) = MFMA GEMMs over a sliding token window.  Operand orders: w_fwd [C_out][k][C_in],
  * w_bwd [C_in][k][C_out] with taps flipped, both `dtype`, produced from the reference layout [C_out][C_in][1][k] by
  * focal_permute_pack / focal_conv_pack_bwd (the flatten + Conv1d(1x1) output layer, ConvModules.py:207-216, is
  * focal_linear_* on weights re-ordered from (c*S + s) to (s*C + c) by focal_permute_pack).
@@ -551,7 +552,7 @@ int focal_bn_stats(const focal_bn_desc* d, const float* z, float* scratch, float
 #define FOCAL_BN_STAT_SLOTS 16
 int focal_conv_fwd_bn(const focal_conv_desc* d, const void* x, const void* w_fwd, const float* bias, float* z,
                       const focal_bn_desc* bn, float* scratch, float* mean_rstd, float* running_mean, float* running_var, void* stream);
-/* Round 6: the sums-only form.  Where focal_conv_fwd_bn_sums_supported(...) != 0 (64 -> 64 channels, k = 3 / 5, bf16, whole 64-row tiles per
+/* Round 6: the sums-only form.  Where focal_conv_fwd_bn_sums_supported(...) != 0 (64 -> 64 channels, k = 3 / 4 / 5, bf16, whole 64-row tiles per
  * statistics group: csrc/conv_ring.hpp), focal_conv_fwd_bn may be called with mean_rstd = NULL (running buffers ignored): the launch then only
  * adds its per-channel sums into `scratch` and ends, and focal_bn_act_fwd_sums -- focal_bn_act_fwd reading `scratch` instead of mean_rstd --
  * finishes the statistics in its prologue (mean_rstd [groups x 2C] out for the backward pass, running buffers updated with d->momentum).  Same
