@@ -127,6 +127,11 @@ class ConvInDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "cin", "I", "S_in", "S_out", "k", "stride", "pad_left", "C")]
 
 
+class Ptr8(C.Structure):
+    """focal_ptr8: up to eight device pointers passed BY VALUE (focal_rows_mean: no pointer table is uploaded)."""
+    _fields_ = [("p", C.c_void_p * 8)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("dtype", "rows", "S", "C_in", "C_out", "k", "dw_workgroups")]
 
@@ -235,6 +240,8 @@ PROTOTYPES = {
     "focal_cast_bf16": (C.c_int, [P, P, C.c_long, P]),
     "focal_conv_in_fwd": (C.c_int, [C.POINTER(ConvInDesc), P, P, P, P, P]),
     "focal_conv_in_bwd_weight": (C.c_int, [C.POINTER(ConvInDesc), P, P, C.c_int, P, P, P]),
+    "focal_conv_in_bwd_data": (C.c_int, [C.POINTER(ConvInDesc), P, C.c_int, P, C.c_float, P, P]),
+    "focal_rows_mean": (C.c_int, [C.c_int, C.c_int, Ptr8, P, P]),
     "focal_permute_pack": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, C.c_int, P]),
     "focal_permute_unpack_add": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P]),
     "focal_pack_multi": (C.c_int, [C.c_int, C.c_int, C.POINTER(PackEntry), P]),

@@ -26,6 +26,16 @@ def is_hot_with_head(name):
     return is_hot(name) or name.startswith(HEAD_PREFIXES)
 
 
+DEEPSENSE_MULTILOC_PREFIX = "mod_extractors."
+
+
+def is_hot_deepsense_multiloc(name):
+    """FOCAL pretraining of DeepSense on a multi-location dataset: the second ConvBlock of every modality (mod_extractors.*, behind
+    the mean over the locations) runs and trains (focal_amd/deepsense_engine.py: DeepSenseMultiLocEncoder); on single-location
+    datasets those parameters are dead (the reference skips the block) and the rule there stays `is_hot`."""
+    return is_hot(name) or name.startswith(DEEPSENSE_MULTILOC_PREFIX)
+
+
 SUPERVISED_DEAD = ("absolute_pos_embed.", "mod_extractors.", "loc_fusion_layers.", "loc_context_layers.", "loc_fusion_layer.", "mod_projectors.")
 
 
@@ -160,6 +170,39 @@ class StageFn(torch.autograd.Function):
         # modality's -- measured -7 % on the four-modality HAR4 step.)
         _join_after_backward(dy.device)
         return None, dx, None, None
+
+
+class MultiStageFn(torch.autograd.Function):
+    """StageFn over an engine that reads several tensors (the L spectra of a multi-location DeepSense modality) and hands no gradient
+    back to any of them: forward(xs, ...) -> (y, saved), backward(saved, dy)."""
+
+    @staticmethod
+    def forward(ctx, anchor, engine, args, *xs):
+        cur = torch.cuda.current_stream(xs[0].device)
+        for x in xs:
+            x.record_stream(cur)
+        y, saved = engine.forward(list(xs), *args)
+        ctx.engine, ctx.saved, ctx.n = engine, saved, len(xs)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        dy.record_stream(torch.cuda.current_stream(dy.device))
+        ctx.engine.backward(ctx.saved, dy)
+        ctx.saved = None
+        _join_after_backward(dy.device)  # (see StageFn.backward)
+        return (None, None, None) + (None,) * ctx.n
+
+
+def run_stage_multi(backbone, engine, xs, *args):
+    if torch.is_grad_enabled():
+        return MultiStageFn.apply(backbone._anchor(xs[0].device), engine, args, *xs)
+    cur = torch.cuda.current_stream(xs[0].device)
+    for x in xs:
+        x.record_stream(cur)
+    y, _ = engine.forward(list(xs), *args)
+    return y
 
 
 def run_stage(backbone, engine, x, *args):

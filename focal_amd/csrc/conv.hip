@@ -449,6 +449,166 @@ extern "C" int focal_conv_in_bwd_weight(const focal_conv_in_desc* d, const float
   return FOCAL_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ in-conv data gradient (cin = 1)
+// dx[tok][s] = scale * sum_c sum_t dz[(tok, s + pad - t)][c] * w[c][t]: the transpose of the 'same' convolution whose input is ONE channel
+// (the second ConvBlock of a multi-location DeepSense reads the mean of the first-level outputs as a [B, 1, I, S] spectrum).
+// One pass over dz in tiles of whole tokens (no tile needs a neighbour's rows):
+//   1. four lanes per row, 16 channels each, two or four 16-byte loads per lane (a quad reads 64 contiguous bytes per instruction); the
+//      lane's 16 x 4 filter taps stay in registers for the whole grid-stride loop; p[t] = sum_c dz[r][c] w[c][t] is finished by two
+//      quad-local DPP adds and lane q parks p[q] in LDS ([4 taps][tile rows], row stride = 8 mod 32 banks: conflict-free writes);
+//   2. one thread per output: dx[s] = scale * sum_t p_t[s + pad - t], rows outside the token dropped; plain stores, no atomics -- the
+//      result is a pure function of the inputs.
+// k > 4 (no shipped config): further passes of four taps each re-read dz and add onto dx; the same thread owns the same outputs in
+// every pass (the tile -> workgroup mapping does not change), so there is still no atomic and no ordering between workgroups.
+#define CID_TAPS 4
+template <typename TZ> struct CidLoad;
+template <> struct CidLoad<float> {  // lane q: channels j * 16 + q * 4 + e (j < 4, e < 4)
+  static __device__ __forceinline__ int channel(int q, int i) { return (i >> 2) * 16 + q * 4 + (i & 3); }
+  static __device__ __forceinline__ void row(const float* p, int q, float (&v)[16]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float4 a = *reinterpret_cast<const float4*>(p + j * 16 + q * 4);
+      v[j * 4] = a.x; v[j * 4 + 1] = a.y; v[j * 4 + 2] = a.z; v[j * 4 + 3] = a.w;
+    }
+  }
+};
+template <> struct CidLoad<bf16_t> {  // lane q: channels j * 32 + q * 8 + e (j < 2, e < 8)
+  static __device__ __forceinline__ int channel(int q, int i) { return (i >> 3) * 32 + q * 8 + (i & 7); }
+  static __device__ __forceinline__ void row(const bf16_t* p, int q, float (&v)[16]) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const bf16x8 a = *reinterpret_cast<const bf16x8*>(p + j * 32 + q * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[j * 8 + e] = (float)a[e];
+    }
+  }
+};
+
+template <typename TZ>
+__global__ __launch_bounds__(256) void conv_in_bwd_data_kernel(const TZ* __restrict__ dz, const float* __restrict__ w, float* __restrict__ dx,
+                                                               int S, int k, int pad, int tokens, int tok_per_tile, int ld, float scale) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];  // [CID_TAPS][ld]
+  const int tid = threadIdx.x, quad = tid >> 2, q = tid & 3;
+  const int tiles = (tokens + tok_per_tile - 1) / tok_per_tile;
+  for (int t0 = 0; t0 < k; t0 += CID_TAPS) {
+    float wr[16][CID_TAPS];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int c = CidLoad<TZ>::channel(q, i);
+#pragma unroll
+      for (int tt = 0; tt < CID_TAPS; ++tt) wr[i][tt] = t0 + tt < k ? w[c * k + t0 + tt] : 0.f;
+    }
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+      const int tok0 = tile * tok_per_tile;
+      const int ntok = tokens - tok0 < tok_per_tile ? tokens - tok0 : tok_per_tile;  // (the tail tile: fewer tokens, same code)
+      const int nrows = ntok * S;
+      const long row0 = (long)tok0 * S;
+      __syncthreads();  // the previous tile's (or pass's) readers are done with the LDS
+      for (int r = quad; r < nrows; r += 64) {  // (a quad's four lanes share r: they stay together)
+        float v[16];
+        CidLoad<TZ>::row(dz + (row0 + r) * 64, q, v);
+        float p[CID_TAPS];
+#pragma unroll
+        for (int tt = 0; tt < CID_TAPS; ++tt) p[tt] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+#pragma unroll
+          for (int tt = 0; tt < CID_TAPS; ++tt) p[tt] += v[i] * wr[i][tt];
+        }
+#pragma unroll
+        for (int tt = 0; tt < CID_TAPS; ++tt) {
+          p[tt] += dpp_f32<0xB1>(p[tt]);  // quad_perm [1,0,3,2]
+          p[tt] += dpp_f32<0x4E>(p[tt]);  // quad_perm [2,3,0,1]: all four lanes hold the row's sum
+        }
+        smem[q * ld + r] = q == 0 ? p[0] : (q == 1 ? p[1] : (q == 2 ? p[2] : p[3]));
+      }
+      __syncthreads();
+      for (int o = tid; o < nrows; o += 256) {
+        const int s = o % S, base = o - s;
+        float acc = 0.f;
+#pragma unroll
+        for (int tt = 0; tt < CID_TAPS; ++tt) {
+          const int src = s + pad - (t0 + tt);
+          if (t0 + tt < k && src >= 0 && src < S) acc += smem[tt * ld + base + src];
+        }
+        if (t0 == 0) dx[row0 + o] = scale * acc;
+        else dx[row0 + o] += scale * acc;
+      }
+    }
+  }
+}
+
+extern "C" int focal_conv_in_bwd_data(const focal_conv_in_desc* d, const void* dz, int dz_dtype, const float* w, float scale, float* dx,
+                                      void* stream) {
+  if (int rc = conv_in_check(d)) return rc;
+  FOCAL_CHECK_ARG(d->cin == 1 && d->stride == 1 && d->S_in == d->S_out,
+                  "conv_in_bwd_data: one input channel, stride 1 and S_in == S_out only (got cin %d, stride %d, S %d -> %d)", d->cin, d->stride,
+                  d->S_in, d->S_out);
+  FOCAL_CHECK_ARG(d->pad_left >= 0 && d->pad_left < d->k, "conv_in_bwd_data: pad_left %d outside [0, k = %d)", d->pad_left, d->k);
+  FOCAL_CHECK_ARG(d->B >= 1 && d->I >= 1 && d->S_out >= 1 && d->S_out <= 2048, "conv_in_bwd_data: B, I >= 1 and 1 <= S <= 2048 (LDS tile of whole tokens)");
+  FOCAL_CHECK_ARG(dz_dtype == FOCAL_F32 || dz_dtype == FOCAL_BF16, "conv_in_bwd_data: bad dz dtype");
+  FOCAL_CHECK_ARG(dz && w && dx, "conv_in_bwd_data: null tensor");
+  FOCAL_CHECK_ARG(((uintptr_t)dz & 15) == 0, "conv_in_bwd_data: dz must be 16-byte aligned");
+  const long tokens_l = (long)d->B * d->I;
+  FOCAL_CHECK_ARG(tokens_l * d->S_out < (1L << 31), "conv_in_bwd_data: more than 2^31 rows");
+  const int S = d->S_out, tokens = (int)tokens_l;
+  const int tpt = S >= 512 ? 1 : 512 / S;             // ~512 rows per tile
+  const int ld = (tpt * S + 31) / 32 * 32 + 8;        // 8 mod 32: the four tap rows of a half-wave's writes fall on disjoint banks
+  const size_t sm = (size_t)CID_TAPS * ld * sizeof(float);  // <= 4 * 2088 * 4 B = 33 KB
+  int blocks = ceil_div(tokens, tpt);
+  if (blocks > 2048) blocks = 2048;
+  hipStream_t st = (hipStream_t)stream;
+  if (dz_dtype == FOCAL_F32)
+    FOCAL_LAUNCH((conv_in_bwd_data_kernel<float>), dim3(blocks), dim3(256), sm, st, (const float*)dz, w, dx, S, d->k, d->pad_left, tokens, tpt, ld, scale);
+  else
+    FOCAL_LAUNCH((conv_in_bwd_data_kernel<bf16_t>), dim3(blocks), dim3(256), sm, st, (const bf16_t*)dz, w, dx, S, d->k, d->pad_left, tokens, tpt, ld, scale);
+  FOCAL_LAUNCH_CHECK();
+  return FOCAL_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mean of L row blocks
+// y[i] = (sum_l xs[l][i]) / L: DeepSense's MeanFusionBlock over the L first-level outputs of a modality.  The L pointers are kernel
+// arguments (focal_ptr8 by value): nothing is uploaded, so the launch can be captured.  float4 body when every pointer is 16-byte
+// aligned, scalar tail (or scalar throughout) otherwise.
+__global__ __launch_bounds__(256) void rows_mean_kernel(focal_ptr8 xs, float* __restrict__ y, int L, long n4, long n) {
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+  const float fl = (float)L;
+  for (long i = gid; i < n4; i += step) {
+    float4 a = reinterpret_cast<const float4*>(xs.p[0])[i];
+#pragma unroll
+    for (int l = 1; l < 8; ++l) {
+      if (l < L) {
+        const float4 b = reinterpret_cast<const float4*>(xs.p[l])[i];
+        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+      }
+    }
+    reinterpret_cast<float4*>(y)[i] = make_float4(a.x / fl, a.y / fl, a.z / fl, a.w / fl);
+  }
+  for (long i = 4 * n4 + gid; i < n; i += step) {
+    float a = xs.p[0][i];
+#pragma unroll
+    for (int l = 1; l < 8; ++l) {
+      if (l < L) a += xs.p[l][i];
+    }
+    y[i] = a / fl;
+  }
+}
+
+extern "C" int focal_rows_mean(int n, int L, focal_ptr8 xs, float* y, void* stream) {
+  FOCAL_CHECK_ARG(n >= 1 && L >= 2 && L <= 8 && y, "rows_mean: n >= 1, 2 <= L <= 8 (got n %d, L %d)", n, L);
+  bool aligned = ((uintptr_t)y & 15) == 0;
+  for (int l = 0; l < L; ++l) {
+    FOCAL_CHECK_ARG(xs.p[l] != nullptr, "rows_mean: null input %d", l);
+    aligned = aligned && ((uintptr_t)xs.p[l] & 15) == 0;
+  }
+  const long n4 = aligned ? n / 4 : 0;
+  int blocks = ceil_div(n4 > 0 ? n4 : n, 256);
+  if (blocks > 1024) blocks = 1024;
+  FOCAL_LAUNCH(rows_mean_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, xs, y, L, n4, (long)n);
+  FOCAL_LAUNCH_CHECK();
+  return FOCAL_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ weight re-layouts
 template <typename TD> __global__ void permute_pack_kernel(const float* __restrict__ src, TD* __restrict__ dst, int A, int Bd, int Cd) {
   const long n = (long)A * Bd * Cd;

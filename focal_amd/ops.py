@@ -912,6 +912,36 @@ def conv_in_bwd_weight(d, x, dz, dw, dbias):
     check(_lib.load().focal_conv_in_bwd_weight(C.byref(d), _p(x), _p(dz), code(dz.dtype), _p(dw), _p(dbias), _stream()))
 
 
+def conv_in_bwd_data(d, dz, w, scale=1.0, out=None):
+    """dx [B*I, S] fp32 = scale * conv_in^T(dz): the in-conv's input gradient where its input is not a leaf (cin = 1, stride 1 only)."""
+    _need_cuda(dz, w)
+    if not dz.is_contiguous() or dz.numel() != d.B * d.I * d.S_out * d.C:
+        raise _lib.FocalHipError(f"conv_in_bwd_data: dz must be a contiguous [{d.B * d.I * d.S_out}, {d.C}] tensor")
+    if w.dtype != torch.float32 or not w.is_contiguous() or w.numel() != d.C * d.cin * d.k:
+        raise _lib.FocalHipError("conv_in_bwd_data: w must be the contiguous fp32 [C, cin, 1, k] filter")
+    dx = torch.empty(d.B * d.I, d.S_in, dtype=torch.float32, device=dz.device) if out is None else out
+    if dx.dtype != torch.float32 or not dx.is_contiguous() or dx.numel() != d.B * d.I * d.S_in:
+        raise _lib.FocalHipError("conv_in_bwd_data: out must be a contiguous fp32 [B*I, S] tensor")
+    check(_lib.load().focal_conv_in_bwd_data(C.byref(d), _p(dz), code(dz.dtype), _p(w), float(scale), _p(dx), _stream()))
+    return dx
+
+
+def rows_mean(xs, out=None):
+    """y = (xs[0] + ... + xs[L-1]) / L for 2 <= L <= 8 equal-shaped contiguous fp32 tensors: one launch, the pointers travel by value."""
+    _need_cuda(*xs)
+    L, n = len(xs), xs[0].numel()
+    if not 2 <= L <= 8:
+        raise _lib.FocalHipError(f"rows_mean: 2 .. 8 inputs (got {L})")
+    if any(x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != n for x in xs):
+        raise _lib.FocalHipError("rows_mean: inputs must be contiguous fp32 tensors of one size")
+    y = torch.empty_like(xs[0]) if out is None else out
+    ptrs = _lib.Ptr8()
+    for i, x in enumerate(xs):
+        ptrs.p[i] = x.data_ptr()
+    check(_lib.load().focal_rows_mean(n, L, ptrs, _p(y), _stream()))
+    return y
+
+
 def permute_pack(src, A, Bd, Cd, dtype):
     """dst[a][c][b] = src[a][b][c], cast to `dtype`."""
     dst = torch.empty(A, Cd, Bd, dtype=dtype, device=src.device)

@@ -1,6 +1,8 @@
 """DeepSense backbone -- same constructor contract, forward signature, module tree and state_dict as the reference
 (models/DeepSense.py), executed on the MI355X HIP kernels: the FOCAL pretraining path (`class_head=False`) and the classifier path
-(`class_head=True`: concatenated features -> class layer) of the finetune and supervised stages; multi-location fusion raises."""
+(`class_head=True`: concatenated features -> class layer) of the finetune and supervised stages.  On a multi-location dataset the
+pretraining path runs the reference's three steps per modality -- one ConvBlock per location, their mean, a second ConvBlock -- in
+front of the GRU (focal_amd/deepsense_engine.py: DeepSenseMultiLocEncoder); the classifier path there raises."""
 import os
 import sys
 
@@ -12,8 +14,8 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from focal_amd import runtime  # noqa: E402
-from focal_amd.backbone import HipBackbone, run_stage  # noqa: E402
-from focal_amd.deepsense_engine import DeepSenseModEncoder  # noqa: E402
+from focal_amd.backbone import HipBackbone, is_hot, is_hot_deepsense_multiloc, run_stage, run_stage_multi  # noqa: E402
+from focal_amd.deepsense_engine import DeepSenseModEncoder, DeepSenseMultiLocEncoder  # noqa: E402
 from focal_amd.head_engine import ClassifierHead  # noqa: E402
 from focal_amd.swin_engine import ProjectorHead  # noqa: E402
 from models.ConvModules import ConvBlock  # noqa: E402
@@ -41,7 +43,15 @@ class DeepSense(HipBackbone):
     def init_encoder(self, args):
         cfg, dcfg = self.config, args.dataset_config
         if self.multi_location_flag:
-            raise NotImplementedError("the MI355X hot path covers single-location datasets (MOD); see DESIGN.md")
+            if self.supervised or getattr(args, "stage", "pretrain") == "finetune":
+                raise NotImplementedError("class_head=True on a multi-location dataset needs the mean fusion and the second ConvBlock in the "
+                                          "classifier path; only FOCAL pretraining of multi-location DeepSense runs them "
+                                          "(focal_amd/deepsense_engine.py)")
+            if cfg["loc_out_channels"] != 128 or cfg["loc_mod_out_channels"] != 128:
+                raise NotImplementedError("multi-location DeepSense covers loc_out_channels = loc_mod_out_channels = 128 (64-channel "
+                                          f"convolution kernels); got {cfg['loc_out_channels']} / {cfg['loc_mod_out_channels']}")
+            if self._hot is is_hot:  # (pretraining: the second ConvBlock of every modality trains)
+                self._hot = is_hot_deepsense_multiloc
         self.loc_mod_extractors = nn.ModuleDict()
         self.geometry = {}
         for loc in self.locations:
@@ -64,6 +74,9 @@ class DeepSense(HipBackbone):
             self.mod_extractors[mod] = ConvBlock(in_channels=1, out_channels=cfg["loc_out_channels"], in_spectrum_len=cfg["loc_mod_out_channels"],
                                                  conv_lens=cfg["loc_conv_lens"], dropout_ratio=cfg["dropout_ratio"],
                                                  num_inter_layers=cfg["loc_conv_inter_layers"])
+        # (built on every dataset, as the reference does; only a multi-location dataset runs them)
+        self.mod_geometry = {mod: dict(self.mod_extractors[mod].geometry, H=cfg["recurrent_dim"], n_rnn=cfg["recurrent_layers"])
+                             for mod in self.modalities}
         self.recurrent_layers = nn.ModuleDict()
         for mod in self.modalities:
             self.recurrent_layers[mod] = RecurrentBlock(in_channel=cfg["loc_out_channels"], out_channel=cfg["recurrent_dim"],
@@ -78,8 +91,15 @@ class DeepSense(HipBackbone):
             self.class_layer = nn.Sequential(nn.Linear(self.sample_dim, n_cls))
         else:
             self.class_layer = nn.Sequential(nn.Linear(self.sample_dim, cfg["fc_dim"]), nn.GELU(), nn.Linear(cfg["fc_dim"], n_cls))
-        self._encoders = {(loc, mod): DeepSenseModEncoder(self, loc, mod, mi)
-                          for loc in self.locations for mi, mod in enumerate(self.modalities)}
+        if self.multi_location_flag:
+            if len(self.modalities) > 8:
+                raise NotImplementedError(f"at most 8 modalities (dropout stream ids); got {len(self.modalities)}")
+            # one engine -- one autograd node -- per modality over its L spectra
+            self._encoders = {(tuple(self.locations), mod): DeepSenseMultiLocEncoder(self, self.locations, mod, mi)
+                              for mi, mod in enumerate(self.modalities)}
+        else:
+            self._encoders = {(loc, mod): DeepSenseModEncoder(self, loc, mod, mi)
+                              for loc in self.locations for mi, mod in enumerate(self.modalities)}
         self._heads = {mod: ProjectorHead(self, mod) for mod in self.modalities}
         self._class_head = ClassifierHead(self)
         self._buffers_by_name = None
@@ -119,7 +139,7 @@ class DeepSense(HipBackbone):
     def forward_encoder(self, freq_x, class_head=True, proj_head=False, defer_join=False, view_index=None, views_in_batch=1):
         if class_head:
             return self.forward_classifier(freq_x)
-        loc = self.locations[0]
+        loc, locs = self.locations[0], tuple(self.locations)
         view = self._fwd_calls
         self._fwd_calls = (self._fwd_calls + 1) & 0xFFFF
         # one HIP stream per modality encoder (see focal_amd/runtime.py: side streams); joined before returning
@@ -141,16 +161,21 @@ class DeepSense(HipBackbone):
                 enc.prepare_packs()  # re-ordered weights for both views' passes: one launch per encoder, before the streams fork
         point = runtime.fork_point(dev)  # every encoder starts from here: none waits for the one launched before it
         order = list(range(len(self.modalities)))
-        order.sort(key=lambda i: -freq_x[loc][self.modalities[i]].numel())  # the heaviest encoder is enqueued first (see SW_Transformer.forward_encoder)
+        # the heaviest encoder is enqueued first (see SW_Transformer.forward_encoder)
+        order.sort(key=lambda i: -sum(freq_x[l][self.modalities[i]].numel() for l in locs))
         for mi in order:
             mod = self.modalities[mi]
             # with one stream per (view, modality) no encoder runs on the caller's stream (index 0): view 2's forks would otherwise
             # wait for the view-1 pass that was enqueued there
             st = runtime.fork_from(dev, (view_index * len(self.modalities) + 1 if view_streams else 0) + mi, point)
             with torch.cuda.stream(st):
-                self._encoders[(loc, mod)].pass_order = view_index if view_streams else None
-                self._encoders[(loc, mod)].views_in_batch = views_in_batch if self.training else 1
-                f = run_stage(self, self._encoders[(loc, mod)], freq_x[loc][mod], view, self.training)
+                enc = self._encoders[(locs if self.multi_location_flag else loc, mod)]
+                enc.pass_order = view_index if view_streams else None
+                enc.views_in_batch = views_in_batch if self.training else 1
+                if self.multi_location_flag:  # the modality's L spectra, in location order, into one node
+                    f = run_stage_multi(self, enc, [freq_x[l][mod] for l in locs], view, self.training)
+                else:
+                    f = run_stage(self, enc, freq_x[loc][mod], view, self.training)
                 out[mod] = run_stage(self, self._heads[mod], f) if proj_head else f
                 out[mod].record_stream(cur)
         if not defer_join:  # FOCAL.forward joins once after both views so that their encoders overlap
@@ -168,7 +193,7 @@ class DeepSense(HipBackbone):
         """`backbone(freq_x, class_head=True)` -> logits (reference: models/DeepSense.py:154-157).  This is the finetuning path: the encoders in front run
         forward-only (finetuning freezes them, general_utils/weight_utils.py:61-80), the head -- the class layer on the concatenated features -- is one
         differentiable node (focal_amd/head_engine.py)."""
-        if self._hot.__name__ == "is_hot":
+        if self._hot.__name__ in ("is_hot", "is_hot_deepsense_multiloc"):
             raise NotImplementedError("class_head=True needs the classifier head in the parameter arena: build the model with "
                                       "args.stage = 'finetune' (or supervised train_mode)")
         if self.supervised:  # supervised training from scratch (train_utils/supervised_train.py): the gradient flows on into the encoders

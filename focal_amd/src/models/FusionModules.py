@@ -7,7 +7,8 @@ import torch.nn as nn
 
 class MeanFusionBlock(nn.Module):
     def forward(self, *a, **k):
-        raise NotImplementedError("DeepSense multi-location fusion (MeanFusionBlock) is outside the MI355X FOCAL pretraining hot path")
+        raise NotImplementedError("MeanFusionBlock is a parameterless container: the mean over the locations runs in "
+                                  "focal_amd/deepsense_engine.py (DeepSenseMultiLocEncoder, focal_rows_mean), not as a torch module")
 
 
 class TransformerFusionBlock(nn.Module):

@@ -492,6 +492,18 @@ typedef struct { int B, cin, I, S_in, S_out, k, stride, pad_left, C; } focal_con
 int focal_conv_in_fwd(const focal_conv_in_desc* d, const float* x, const float* w, const float* bias, float* z, void* stream);
 int focal_conv_in_bwd_weight(const focal_conv_in_desc* d, const float* x, const void* dz, int dz_dtype, float* dw, float* dbias,
                              void* stream);
+/* The in-conv's data gradient where its input is NOT a leaf: the second ConvBlock of a multi-location DeepSense (mod_extractors.*) reads
+ * the mean of the L first-level outputs as a one-channel spectrum.  cin == 1, stride == 1, S_in == S_out, C == 64, 1 <= k <= 192 (the
+ * reference hard-codes in_channels = 1 there); anything else is FOCAL_EINVAL before any launch.
+ *   dx[b, 0, i, s] = scale * sum_{c < 64} sum_{t < k} dz[(b, i, s + pad_left - t), c] * w[c, 0, 0, t],  rows outside [0, S) dropped
+ * dz [B*I*S, 64] channel-last, fp32 or bf16 (dz_dtype), 16-byte aligned; w the fp32 master [64][1][1][k]; fp32 accumulation; dx fp32
+ * [B*I, S], written (not accumulated).  One pass over dz, no atomics: bit-identical from call to call.  `scale` carries the 1 / L of
+ * the mean's backward: the one dx is then the output gradient of all L first-level blocks. */
+int focal_conv_in_bwd_data(const focal_conv_in_desc* d, const void* dz, int dz_dtype, const float* w, float scale, float* dx, void* stream);
+/* y[i] = (sum_{l < L} xs.p[l][i]) / L, fp32, 2 <= L <= 8 (DeepSense's MeanFusionBlock over a modality's L first-level outputs).  The
+ * L device pointers travel by value: no pointer table is uploaded, the launch is capturable.  One launch. */
+typedef struct { const float* p[8]; } focal_ptr8;
+int focal_rows_mean(int n, int L, focal_ptr8 xs, float* y, void* stream);
 /* [1,k] "same" convs (any k >= 1; k - 1 zeros in all, (k - 1) / 2 on the left and the rest on the right, as torch pads an even filter;
  * the data gradient runs the flipped taps with k / 2 on the left) = MFMA GEMMs over a sliding token window.  Operand orders: w_fwd [C_out][k][C_in],
  * w_bwd [C_in][k][C_out] with taps flipped, both `dtype`, produced from the reference layout [C_out][C_in][1][k] by
