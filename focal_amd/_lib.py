@@ -226,6 +226,7 @@ PROTOTYPES = {
     "focal_loc_unstack_add": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P]),
     "focal_loc_mean_bwd_add": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P]),
     "focal_cross_entropy": (C.c_int, [C.c_int, C.c_int, P, P, P, P, P]),
+    "focal_eval_accumulate": (C.c_int, [C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "focal_small_linear_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P]),
     "focal_small_linear_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "focal_loss_head_workspace": (C.c_size_t, [C.POINTER(LossDesc)]),

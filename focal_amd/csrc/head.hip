@@ -111,6 +111,71 @@ extern "C" int focal_cross_entropy(int B, int C, const float* logits, const long
   return FOCAL_OK;
 }
 
+// ---- evaluation accumulator: what the validation / test loop needs from a batch, left on the device.  conf [C*C + 1] ints:
+// conf[label * C + pred] counts, the last word counts rejected rows (label or prediction outside [0, C)); acc [2] doubles:
+// {sum of per-batch mean losses, number of batches}.  Logits mode: the batch loss is cross_entropy_kernel's loss[0] bit for bit --
+// the same rows per thread, the same fmaxf / expf / logf sequence, the same tree --, which is why this is ONE workgroup of 256
+// threads however large B is; the prediction is the first index of the row maximum.  Prediction mode (logits == NULL): only the
+// matrix.  The batch is counted into an LDS tile laid out like conf and added with plain loads and stores: one workgroup, and
+// batches are ordered by the stream, so nothing else writes conf or acc while this runs.
+#define EVAL_MAX_C 64
+__global__ __launch_bounds__(256) void eval_accumulate_kernel(const float* __restrict__ logits, const long* __restrict__ preds_in,
+                                                              const long* __restrict__ labels, double* __restrict__ acc,
+                                                              int* __restrict__ conf, long* __restrict__ preds_out, int B, int C) {
+  __shared__ float part[256];
+  __shared__ int tile[EVAL_MAX_C * EVAL_MAX_C + 1];
+  const int cells = C * C;
+  for (int i = threadIdx.x; i <= cells; i += 256) tile[i] = 0;
+  __syncthreads();
+  float sum = 0.f;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const long y = labels[b];
+    const bool y_ok = y >= 0 && y < C;
+    long p;
+    if (logits) {
+      const float* row = logits + (long)b * C;
+      float mx = row[0], best = row[0];
+      int arg = 0;
+      for (int c = 1; c < C; ++c) {
+        mx = fmaxf(mx, row[c]);
+        if (row[c] > best) { best = row[c]; arg = c; }
+      }
+      float den = 0.f;
+      for (int c = 0; c < C; ++c) den += expf(row[c] - mx);
+      if (y_ok) sum += logf(den) + mx - row[y];  // (a rejected label never indexes the row)
+      p = arg;
+    } else {
+      p = preds_in[b];
+    }
+    if (preds_out) preds_out[b] = p;
+    atomicAdd(&tile[y_ok && p >= 0 && p < C ? (int)y * C + (int)p : cells], 1);
+  }
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  for (int i = threadIdx.x; i <= cells; i += 256) {
+    const int n = tile[i];
+    if (n) conf[i] += n;
+  }
+  if (threadIdx.x == 0 && logits) {
+    acc[0] += (double)(part[0] / (float)B);
+    acc[1] += 1.0;
+  }
+}
+
+extern "C" int focal_eval_accumulate(int B, int C, const float* logits, const long* preds_in, const long* labels, double* acc,
+                                     int* conf, long* preds_out, void* stream) {
+  FOCAL_CHECK_ARG(B >= 1 && C >= 1 && C <= EVAL_MAX_C, "eval_accumulate: need B >= 1 and 1 <= C <= %d (got B=%d C=%d)", EVAL_MAX_C, B, C);
+  FOCAL_CHECK_ARG((logits != nullptr) != (preds_in != nullptr), "eval_accumulate: exactly one of logits / preds_in");
+  FOCAL_CHECK_ARG(labels && acc && conf, "eval_accumulate: null tensor");
+  FOCAL_LAUNCH(eval_accumulate_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, preds_in, labels, acc, conf, preds_out, B, C);
+  FOCAL_LAUNCH_CHECK();
+  return FOCAL_OK;
+}
+
 // ---- class layer: nn.Linear(K -> n_cls) with a handful of outputs (7 vehicle classes): too narrow for the 16-column MFMA
 // tiles (and n_cls is not a multiple of the GEMM family's vector width), and a few hundred KFLOP in any case.  fp32 VALU.
 // y[b][n] = bias[n] + sum_k x[b][k] w[n][k]: one wave per (b, n), lanes over k.

@@ -1205,6 +1205,54 @@ def cross_entropy(logits, labels):
     return loss, dlogits
 
 
+def eval_accumulate(acc, conf, labels, logits=None, preds=None, preds_out=None):
+    """One batch into the evaluation accumulators (focal_eval_accumulate), no host read.  Caller-owned: acc fp64 [2] = {sum of the
+    per-batch mean losses, batches}, conf int32 [C*C + 1] = the confusion matrix conf[label * C + pred] and, last, the count of rows
+    whose label or prediction lies outside [0, C).  Exactly one of logits (fp32 [B, C]; the loss and the argmax are taken in the
+    kernel) and preds ([B] class indices; the matrix alone).  preds_out (int64 [B]) receives the predictions.  The inputs (labels,
+    logits, preds) are converted to int64 / fp32 and copied when they are strided; acc, conf and preds_out are written in place and
+    must be contiguous."""
+    labels = labels.long().contiguous()
+    logits = None if logits is None else logits.float().contiguous()
+    preds = None if preds is None else preds.long().contiguous()
+    _need_cuda(acc, conf, labels, logits, preds, preds_out)
+    if acc.dtype != torch.float64 or acc.numel() != 2 or conf.dtype != torch.int32:
+        raise _lib.FocalHipError("eval_accumulate: acc must be fp64 [2] and conf int32 [C*C + 1]")
+    Cn = math.isqrt(max(conf.numel() - 1, 0))
+    if Cn * Cn + 1 != conf.numel():
+        raise _lib.FocalHipError(f"eval_accumulate: conf holds {conf.numel()} words, which is not C*C + 1 for any C")
+    B = labels.numel()
+    if logits is not None and tuple(logits.shape) != (B, Cn):
+        raise _lib.FocalHipError(f"eval_accumulate: logits {tuple(logits.shape)} against {B} labels and a {Cn} x {Cn} matrix")
+    if preds is not None and preds.numel() != B:
+        raise _lib.FocalHipError(f"eval_accumulate: {preds.numel()} predictions against {B} labels")
+    if preds_out is not None and (preds_out.dtype != torch.int64 or preds_out.numel() != B):
+        raise _lib.FocalHipError("eval_accumulate: preds_out must be int64 [B]")
+    check(_lib.load().focal_eval_accumulate(B, Cn, _p(logits), _p(preds), _p(labels), _p(acc), _p(conf), _p(preds_out), _stream()))
+
+
+class EvalState:
+    """Loss and confusion matrix of one evaluation pass, kept on the device: `add` is one launch per batch, `read` the pass's one
+    synchronising call."""
+
+    def __init__(self, num_classes, device):
+        self.C = int(num_classes)
+        self.acc = torch.zeros(2, dtype=torch.float64, device=device)
+        self.conf = torch.zeros(self.C * self.C + 1, dtype=torch.int32, device=device)
+
+    def add(self, labels, logits=None, preds=None, preds_out=None):
+        eval_accumulate(self.acc, self.conf, labels, logits=logits, preds=preds, preds_out=preds_out)
+
+    def read(self):
+        """(sum of the per-batch mean losses, number of batches, confusion matrix as int64 numpy [C, C]); one device-to-host copy."""
+        words = torch.cat([self.acc.view(torch.int32), self.conf]).cpu().numpy()
+        loss_sum, n_batches = words[:4].view("float64")
+        rejected, cells = int(words[-1]), self.C * self.C
+        if rejected:
+            raise ValueError(f"{rejected} evaluated rows carry a label or a prediction outside [0, {self.C})")
+        return float(loss_sum), int(n_batches), words[4:4 + cells].astype("int64").reshape(self.C, self.C)
+
+
 def mean_time(x, B, T, D):
     y = torch.empty(B, D, dtype=torch.float32, device=x.device)
     check(_lib.load().focal_mean_time(B, T, D, _p(x), _p(y), _stream()))

@@ -3,7 +3,8 @@ import torch
 
 
 def load_model_weight(args, model, weight_file, load_class_layer=True):
-    trained = torch.load(weight_file, map_location=args.device)
+    """`weight_file`: the checkpoint's path, or its state dict when the caller has loaded it already (test.py looks at the names first)."""
+    trained = weight_file if isinstance(weight_file, dict) else torch.load(weight_file, map_location=args.device)
     own = model.state_dict()
     picked = {k: v for k, v in trained.items() if k in own and (load_class_layer or "class_layer" not in k)}
     own.update(picked)

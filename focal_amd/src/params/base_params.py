@@ -9,7 +9,7 @@ def parse_base_args(option="train"):
     p.add_argument("-learn_framework", type=str, default="no", help="No/Contrastive/Predictive/Reconstruction learning framework to use")
     p.add_argument("-stage", type=str, default="pretrain", help="The pretrain/finetune, used for foundation model only.")
     p.add_argument("-model", type=str, default="DeepSense", help="The backbone classification model to use.")
-    p.add_argument("-model_weight", type=str, default=None, help="Specify the model weight path to evaluate.")
+    p.add_argument("-model_weight", type=str, default=None, help="Specify the model weight path to evaluate: the folder that holds the checkpoint; [build extension] or the checkpoint file itself.")
     p.add_argument("-batch_size", type=int, default=None, help="Specify the batch size for training.")
     p.add_argument("-label_ratio", type=float, default=1.0, help="Only used in supervised training or finetune stage.")
     p.add_argument("-gpu", type=str, default="0", help="Specify which GPU to use ('cpu' is rejected: HIP path only).")

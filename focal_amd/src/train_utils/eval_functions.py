@@ -9,6 +9,8 @@ from sklearn.metrics import accuracy_score, confusion_matrix, f1_score
 from train_utils.knn import extract_sample_features
 from train_utils.loss_calc_utils import calc_pretrain_loss
 
+from focal_amd import ops  # noqa: E402  (train_utils.knn has put the repository root on sys.path)
+
 
 def eval_task_metrics(args, labels, predictions):
     if args.task in {"distance_classification", "speed_classification"}:
@@ -25,19 +27,50 @@ def eval_task_metrics(args, labels, predictions):
     return mean_acc, mean_f1, conf
 
 
+def metrics_from_confusion(args, conf):
+    """`eval_task_metrics` from the confusion matrix alone (conf[label, prediction] counts over ALL classes of the task, pure numpy):
+    the classes that count are the ones seen as a label or as a prediction -- sklearn's sorted union --, macro-F1 is taken over them
+    and the returned matrix is `conf` restricted to them."""
+    conf = np.asarray(conf, dtype=np.int64)
+    total = conf.sum()
+    true_sum, pred_sum, tp = conf.sum(axis=1), conf.sum(axis=0), np.diag(conf)
+    if args.task in {"distance_classification", "speed_classification"}:
+        num_classes = args.dataset_config[args.task]["num_classes"]
+        lab = np.arange(conf.shape[0], dtype=np.float64)[:, None]
+        pred = np.arange(conf.shape[1], dtype=np.float64)[None, :]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cell = 1 - (np.abs(lab - pred) / np.maximum(lab, (num_classes - 1) - lab))
+        mean_acc = float((np.nan_to_num(cell, nan=1.0) * conf)[conf > 0].sum() / total)
+    else:
+        mean_acc = float(tp.sum() / total)
+    seen = np.flatnonzero(true_sum + pred_sum)
+    mean_f1 = float(np.average(2.0 * tp[seen] / (true_sum[seen] + pred_sum[seen])))  # (zero_division never applies to a seen class)
+    return mean_acc, mean_f1, conf[np.ix_(seen, seen)]
+
+
 def eval_supervised_model(args, classifier, augmenter, dataloader, loss_func):
-    """Loss and task metrics of a classifier (reference :29-62)."""
+    """Loss and task metrics of a classifier (reference :29-62).  Loss and confusion matrix stay on the device (ops.EvalState: one
+    launch per batch, whose batch loss is `CrossEntropyLoss`'s bit for bit); the host reads them once, after the loop.
+    `loss_func` is not called: it names the loss, and the one built is the project's `models.loss.CrossEntropyLoss` (mean reduction, no
+    class weights, no label smoothing), which is what init_loss_func hands the finetune / supervised stages.  Anything else is refused,
+    never scored as plain cross-entropy."""
+    from models.loss import CrossEntropyLoss
+    if not isinstance(loss_func, CrossEntropyLoss):
+        raise TypeError(f"eval_supervised_model accumulates models.loss.CrossEntropyLoss on the device; {type(loss_func).__name__} is not built")
     classifier.eval()
-    losses, preds, labs = [], [], []
+    state = None
     with torch.no_grad():
         for time_loc_inputs, labels in dataloader:
             freq_loc_inputs, labels = augmenter.forward("no", time_loc_inputs, labels)
             logits = classifier(freq_loc_inputs)
-            losses.append(loss_func(logits, labels).item())
             labels = labels.argmax(dim=1) if labels.dim() > 1 else labels
-            preds.append(logits.argmax(dim=1).cpu().numpy())
-            labs.append(labels.cpu().numpy())
-    return float(np.mean(losses)), eval_task_metrics(args, np.concatenate(labs), np.concatenate(preds))
+            if state is None:
+                state = ops.EvalState(logits.shape[1], logits.device)
+            state.add(labels.to(logits.device), logits=logits)
+    if state is None:
+        raise ValueError("eval_supervised_model: the loader yielded no batch")
+    loss_sum, n_batches, conf = state.read()
+    return loss_sum / n_batches, metrics_from_confusion(args, conf)
 
 
 def eval_pretrained_model(args, default_model, estimator, augmenter, dataloader, loss_func):
@@ -45,12 +78,16 @@ def eval_pretrained_model(args, default_model, estimator, augmenter, dataloader,
     feats, labels, losses = [], [], []
     with torch.no_grad():
         for time_loc_inputs, label in dataloader:
-            label = label.argmax(dim=1) if label.dim() > 1 else label
-            labels.append(label.cpu().numpy())
-            losses.append(calc_pretrain_loss(args, default_model, augmenter, loss_func, time_loc_inputs).item())
+            labels.append(label.argmax(dim=1) if label.dim() > 1 else label)
+            losses.append(calc_pretrain_loss(args, default_model, augmenter, loss_func, time_loc_inputs).detach().reshape(1))
             feats.append(extract_sample_features(args, default_model.backbone, augmenter.forward("no", time_loc_inputs)))
-    predictions = estimator.predict(torch.cat(feats)).cpu().numpy()
-    return float(np.mean(losses)), eval_task_metrics(args, np.concatenate(labels), predictions)
+    if not feats:
+        raise ValueError("eval_pretrained_model: the loader yielded no batch")
+    predictions = estimator.predict(torch.cat(feats))
+    state = ops.EvalState(args.dataset_config[args.task]["num_classes"], predictions.device)
+    state.add(torch.cat(labels).to(predictions.device), preds=predictions)
+    mean_loss = float(np.mean(torch.cat(losses).double().cpu().numpy()))  # the per-batch losses: one read, averaged in fp64
+    return mean_loss, metrics_from_confusion(args, state.read()[2])
 
 
 def val_and_logging(args, epoch, model, augmenter, val_loader, test_loader, loss_func, train_loss, estimator=None):

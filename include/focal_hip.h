@@ -628,6 +628,17 @@ int focal_fusion_attn_fwd(int B, int M, int E, int heads, const float* q, const 
 int focal_fusion_attn_bwd(int B, int M, int E, int heads, const float* q, const float* kv, const float* probs, const float* weights,
                           const float* dout, float* dq, float* dkv, void* stream);
 int focal_cross_entropy(int B, int C, const float* logits, const long* labels, float* loss, float* dlogits, void* stream);
+/* The evaluation loop's accumulator (train_utils/eval_functions.py:29-62): one launch per batch, no host read.  Exactly one of
+ * logits (fp32 [B, C]) and preds_in ([B]) is given.  Logits mode: acc[0] += the batch's mean cross-entropy -- bit-identical to
+ * focal_cross_entropy's loss[0] on the same arguments --, acc[1] += 1 (the mean of acc[0] over acc[1] batches is the reference's
+ * np.mean(classifier_loss_list): per batch, not per sample); the prediction of a row is the first index of its maximum.
+ * Prediction mode: the matrix alone (the KNN path of pretraining validation).  conf is int [C*C + 1]: conf[label*C + pred] += 1
+ * per row; a row whose label or prediction is outside [0, C) adds to neither the matrix nor the loss, never indexes logits with
+ * the label, and adds 1 to conf[C*C] -- the caller reads that word with the matrix and refuses the result when it is not 0.
+ * preds_out ([B] or NULL) receives the predictions.  1 <= C <= 64, B >= 1.  One workgroup: launches that share acc / conf must
+ * be ordered by their stream. */
+int focal_eval_accumulate(int B, int C, const float* logits, const long* preds_in, const long* labels, double* acc, int* conf,
+                          long* preds_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ location fusion (SW_Transformer)
  * Multi-location datasets: per modality, the L location features of a sample are a sequence of L tokens that runs through
