@@ -15,7 +15,7 @@ EPI_NONE, EPI_RESIDUAL, EPI_RELU, EPI_GELU = 0, 1, 2, 3
 BN_EVAL, BN_TRAIN, BN_PARTIAL, BN_FINALIZE = 0, 1, 2, 3
 BN_SCRATCH_ZEROED = 16  # OR into the mode: the scratch already holds zeros (no memset launch)
 BN_STAT_SLOTS = 16      # focal_conv_fwd_bn: column sums are spread over this many slots of the scratch
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class DropDesc(C.Structure):
@@ -32,13 +32,9 @@ class AugDesc(C.Structure):
                 ("phase_sin", C.c_float)]
 
 
-class FftProblem(C.Structure):
-    _fields_ = [("d", FFTDesc), ("has_aug", C.c_int), ("aug", AugDesc), ("x", C.c_void_p), ("twiddle", C.c_void_p), ("out", C.c_void_p),
-                ("plan", C.c_void_p), ("x_warped", C.c_void_p)]
-
-
-VIEW_MAX_KNOTS, VIEW_MAX_POOL, VIEW_MAX_SLOTS = 16, 8, 8
-VIEW_NONE, VIEW_NEGATION, VIEW_SCALING, VIEW_HFLIP, VIEW_PERMUTATION, VIEW_PHASE_SHIFT, VIEW_MAG_WARP, VIEW_TIME_WARP = range(8)
+VIEW_MAX_KNOTS, VIEW_MAX_POOL, VIEW_MAX_SLOTS, VIEW_MAX_CHANNELS = 16, 16, 8, 16
+(VIEW_NONE, VIEW_NEGATION, VIEW_SCALING, VIEW_HFLIP, VIEW_PERMUTATION, VIEW_PHASE_SHIFT, VIEW_MAG_WARP, VIEW_TIME_WARP, VIEW_JITTER,
+ VIEW_CHANNEL_SHUFFLE, VIEW_TIME_MASK, VIEW_FREQ_MASK) = range(12)
 
 
 class ViewPlan(C.Structure):
@@ -46,32 +42,24 @@ class ViewPlan(C.Structure):
                 ("knots", C.c_float * VIEW_MAX_KNOTS)]
 
 
-class ViewPool(C.Structure):
-    _fields_ = [("n_aug", C.c_int), ("kind", C.c_int * VIEW_MAX_POOL), ("prob", C.c_float * VIEW_MAX_POOL), ("scaling_std", C.c_float),
-                ("mag_magnitude", C.c_float), ("time_magnitude", C.c_float), ("mag_order", C.c_int), ("time_order", C.c_int),
-                ("intervals", C.c_int * VIEW_MAX_SLOTS)]
-
-
-# ---- jitter / channel shuffle / time mask / freq mask: additions beside the records above (include/focal_hip.h: focal_view_extra)
-VIEW_MAX_POOL_EX, VIEW_MAX_CHANNELS = 16, 16
-VIEW_JITTER, VIEW_CHANNEL_SHUFFLE, VIEW_TIME_MASK, VIEW_FREQ_MASK = 8, 9, 10, 11
-
-
 class ViewExtra(C.Structure):
+    """jitter / channel shuffle / time mask / freq mask of one transform (include/focal_hip.h: focal_view_extra); zero = the identity."""
     _fields_ = [("jitter_std", C.c_float), ("jitter_key", C.c_uint32), ("use_chan", C.c_int), ("chan", C.c_int * VIEW_MAX_CHANNELS),
                 ("tmask_lo", C.c_int), ("tmask_n", C.c_int), ("fmask_lo", C.c_int), ("fmask_n", C.c_int)]
 
 
-class ViewPoolEx(C.Structure):
-    _fields_ = [("n_aug", C.c_int), ("kind", C.c_int * VIEW_MAX_POOL_EX), ("prob", C.c_float * VIEW_MAX_POOL_EX), ("scaling_std", C.c_float),
+class ViewPool(C.Structure):
+    _fields_ = [("n_aug", C.c_int), ("kind", C.c_int * VIEW_MAX_POOL), ("prob", C.c_float * VIEW_MAX_POOL), ("scaling_std", C.c_float),
                 ("mag_magnitude", C.c_float), ("time_magnitude", C.c_float), ("mag_order", C.c_int), ("time_order", C.c_int),
                 ("intervals", C.c_int * VIEW_MAX_SLOTS), ("jitter_std", C.c_float * VIEW_MAX_SLOTS), ("channels", C.c_int * VIEW_MAX_SLOTS),
                 ("tmask_d", C.c_int * VIEW_MAX_SLOTS), ("tmask_i", C.c_int * VIEW_MAX_SLOTS), ("fmask_w", C.c_int * VIEW_MAX_SLOTS),
                 ("fmask_n", C.c_int * VIEW_MAX_SLOTS)]
 
 
-class FftProblemEx(C.Structure):
-    _fields_ = [("p", FftProblem), ("has_extra", C.c_int), ("extra", ViewExtra), ("extra_dev", C.c_void_p), ("noise_salt", C.c_uint32)]
+class FftProblem(C.Structure):
+    _fields_ = [("d", FFTDesc), ("has_aug", C.c_int), ("aug", AugDesc), ("x", C.c_void_p), ("twiddle", C.c_void_p), ("out", C.c_void_p),
+                ("plan", C.c_void_p), ("x_warped", C.c_void_p), ("has_extra", C.c_int), ("extra", ViewExtra), ("extra_dev", C.c_void_p),
+                ("noise_salt", C.c_uint32)]
 
 
 class WarpProblem(C.Structure):
@@ -171,10 +159,7 @@ PROTOTYPES = {
     "focal_augment_fft_fwd": (C.c_int, [C.POINTER(FFTDesc), C.POINTER(AugDesc), P, P, P, P]),
     "focal_fft_realpack_multi": (C.c_int, [C.c_int, C.POINTER(FftProblem), P]),
     "focal_warp_fwd": (C.c_int, [C.c_int, C.c_int, P, P, P, P, C.c_int, P, P]),
-    "focal_view_draw": (C.c_int, [C.POINTER(ViewPool), C.c_int, C.c_int, P, C.c_uint32, P, P]),
-    "focal_view_draw_shared": (C.c_int, [C.POINTER(ViewPool), C.c_int, C.c_int, P, C.c_uint32, P, P]),
-    "focal_view_draw_ex": (C.c_int, [C.POINTER(ViewPoolEx), C.c_int, C.c_int, P, C.c_int, C.c_uint32, P, P, P]),
-    "focal_fft_realpack_multi_ex": (C.c_int, [C.c_int, C.POINTER(FftProblemEx), P]),
+    "focal_view_draw": (C.c_int, [C.POINTER(ViewPool), C.c_int, C.c_int, P, C.c_int, C.c_uint32, P, P, P]),
     "focal_warp_plan_multi": (C.c_int, [C.c_int, C.POINTER(WarpProblem), P, P]),
     "focal_mixup_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
     "focal_pad_patch_embed_ln_fwd": (C.c_int, [C.POINTER(EmbedDesc), P, P, P, P, P, P, P]),

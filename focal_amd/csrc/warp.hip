@@ -65,7 +65,7 @@ extern "C" int focal_warp_fwd(int rows, int L, const float* x, const float* mult
   return FOCAL_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ view draws on the device (round 5)
+// ------------------------------------------------------------------------------------------------ view draws on the device
 // Everything the reference's augmenter classes draw on the host per view (include/focal_hip.h: focal_view_draw), from a counter RNG:
 // draw i of a (view, slot) key = focal_mix32(key + i * odd constant); the key mixes the device seed word (advanced by the optimizer every
 // step), the caller's stream id, the view and the slot.  One thread per (view, slot); the kernel is a handful of scalar operations.
@@ -75,12 +75,13 @@ __device__ __forceinline__ float vd_normal(uint32_t key, uint32_t i) {  // Box-M
   return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
-// `advance` (focal_view_draw_shared): the seed word is the draw's OWN state -- one every data-parallel rank holds a copy of, so that the global
-// batch gets one augmenter / coin / permutation / scale / phase per view as the reference's batch does -- and the kernel moves it on after
-// everybody has read it (the word the optimizer advances keys the per-rank dropout streams and stays per-rank).
-// (one body for both pool forms: EX = focal_view_pool_ex and an extras array -- the old kinds take the same draws and write the same bytes)
-template <class POOL, bool EX>
-__device__ __forceinline__ void view_draw_body(const POOL& pool, int n_views, int n_slots, uint32_t* seed, uint32_t stream_id,
+// `advance`: the seed word is the draw's OWN state -- one every data-parallel rank holds a copy of, so that the global batch gets one
+// augmenter / coin / permutation / scale / phase per view as the reference's batch does -- and the kernel moves it on after everybody has
+// read it (the word the optimizer advances keys the per-rank dropout streams and stays per-rank).
+// EX = an extras array is written beside the plans.  Two instantiations, so that a draw without extras pays nothing for them; the plan
+// bytes are the same either way (the kinds 0 .. 7 take the same draws).
+template <bool EX>
+__device__ __forceinline__ void view_draw_body(const focal_view_pool& pool, int n_views, int n_slots, uint32_t* seed, uint32_t stream_id,
                                                focal_view_plan* __restrict__ plans, focal_view_extra* __restrict__ extras, int advance) {
   __shared__ int s_perm[64][FOCAL_AUG_MAX_INTERVALS + 1];
   const int t = threadIdx.x;
@@ -179,64 +180,47 @@ __device__ __forceinline__ void view_draw_body(const POOL& pool, int n_views, in
 
 __global__ __launch_bounds__(64) void view_draw_kernel(const focal_view_pool pool, int n_views, int n_slots, uint32_t* seed,
                                                        uint32_t stream_id, focal_view_plan* __restrict__ plans, int advance) {
-  view_draw_body<focal_view_pool, false>(pool, n_views, n_slots, seed, stream_id, plans, nullptr, advance);
+  view_draw_body<false>(pool, n_views, n_slots, seed, stream_id, plans, nullptr, advance);
 }
-__global__ __launch_bounds__(64) void view_draw_ex_kernel(const focal_view_pool_ex pool, int n_views, int n_slots, uint32_t* seed,
-                                                          uint32_t stream_id, focal_view_plan* __restrict__ plans,
-                                                          focal_view_extra* __restrict__ extras, int advance) {
-  view_draw_body<focal_view_pool_ex, true>(pool, n_views, n_slots, seed, stream_id, plans, extras, advance);
+__global__ __launch_bounds__(64) void view_draw_extras_kernel(const focal_view_pool pool, int n_views, int n_slots, uint32_t* seed,
+                                                              uint32_t stream_id, focal_view_plan* __restrict__ plans,
+                                                              focal_view_extra* __restrict__ extras, int advance) {
+  view_draw_body<true>(pool, n_views, n_slots, seed, stream_id, plans, extras, advance);
 }
 
-static int view_draw_launch(const focal_view_pool* pool, int n_views, int n_slots, uint32_t* seed, uint32_t stream_id,
-                            focal_view_plan* plans, int advance, void* stream) {
-  FOCAL_CHECK_ARG(pool && plans && n_views >= 1 && n_slots >= 1 && n_slots <= FOCAL_VIEW_MAX_SLOTS && n_views * n_slots <= 64,
-                  "view_draw: 1 .. %d slots, at most 64 (view, slot) pairs", FOCAL_VIEW_MAX_SLOTS);
+static int view_pool_check(const focal_view_pool* pool, int n_slots, bool with_extras) {
   FOCAL_CHECK_ARG(pool->n_aug >= 1 && pool->n_aug <= FOCAL_VIEW_MAX_POOL, "view_draw: pool of 1 .. %d augmenters", FOCAL_VIEW_MAX_POOL);
   for (int i = 0; i < pool->n_aug; ++i) {
-    FOCAL_CHECK_ARG(pool->kind[i] >= FOCAL_VIEW_NONE && pool->kind[i] <= FOCAL_VIEW_TIME_WARP, "view_draw: unknown augmenter kind %d", pool->kind[i]);
-    const int ord = pool->kind[i] == FOCAL_VIEW_MAG_WARP ? pool->mag_order : pool->kind[i] == FOCAL_VIEW_TIME_WARP ? pool->time_order : 2;
-    FOCAL_CHECK_ARG(ord >= 2 && 3 * (ord - 1) + 1 <= FOCAL_VIEW_MAX_KNOTS, "view_draw: spline order %d needs more than %d knots", ord, FOCAL_VIEW_MAX_KNOTS);
-  }
-  FOCAL_LAUNCH(view_draw_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *pool, n_views, n_slots, seed, stream_id, plans, advance);
-  FOCAL_LAUNCH_CHECK();
-  return FOCAL_OK;
-}
-
-extern "C" int focal_view_draw_ex(const focal_view_pool_ex* pool, int n_views, int n_slots, uint32_t* state, int advance, uint32_t stream_id,
-                                  focal_view_plan* plans, focal_view_extra* extras, void* stream) {
-  FOCAL_CHECK_ARG(pool && plans && extras && n_views >= 1 && n_slots >= 1 && n_slots <= FOCAL_VIEW_MAX_SLOTS && n_views * n_slots <= 64,
-                  "view_draw_ex: 1 .. %d slots, at most 64 (view, slot) pairs", FOCAL_VIEW_MAX_SLOTS);
-  FOCAL_CHECK_ARG(!advance || state != nullptr, "view_draw_ex: advance needs the view state (4 words: {seed, draw count, 0, 0})");
-  FOCAL_CHECK_ARG(pool->n_aug >= 1 && pool->n_aug <= FOCAL_VIEW_MAX_POOL_EX, "view_draw_ex: pool of 1 .. %d augmenters", FOCAL_VIEW_MAX_POOL_EX);
-  for (int i = 0; i < pool->n_aug; ++i) {
     const int kd = pool->kind[i];
-    FOCAL_CHECK_ARG(kd >= FOCAL_VIEW_NONE && kd <= FOCAL_VIEW_FREQ_MASK, "view_draw_ex: unknown augmenter kind %d", kd);
+    FOCAL_CHECK_ARG(kd >= FOCAL_VIEW_NONE && kd <= FOCAL_VIEW_FREQ_MASK, "view_draw: unknown augmenter kind %d", kd);
+    FOCAL_CHECK_ARG(with_extras || kd < FOCAL_VIEW_JITTER, "view_draw: augmenter kind %d travels in a focal_view_extra: the draw needs an extras array", kd);
     const int ord = kd == FOCAL_VIEW_MAG_WARP ? pool->mag_order : kd == FOCAL_VIEW_TIME_WARP ? pool->time_order : 2;
-    FOCAL_CHECK_ARG(ord >= 2 && 3 * (ord - 1) + 1 <= FOCAL_VIEW_MAX_KNOTS, "view_draw_ex: spline order %d needs more than %d knots", ord, FOCAL_VIEW_MAX_KNOTS);
+    FOCAL_CHECK_ARG(ord >= 2 && 3 * (ord - 1) + 1 <= FOCAL_VIEW_MAX_KNOTS, "view_draw: spline order %d needs more than %d knots", ord, FOCAL_VIEW_MAX_KNOTS);
     for (int s = 0; s < n_slots; ++s) {
-      if (kd == FOCAL_VIEW_JITTER) FOCAL_CHECK_ARG(pool->jitter_std[s] >= 0.f, "view_draw_ex: jitter std of slot %d is negative", s);
+      if (kd == FOCAL_VIEW_JITTER) FOCAL_CHECK_ARG(pool->jitter_std[s] >= 0.f, "view_draw: jitter std of slot %d is negative", s);
       if (kd == FOCAL_VIEW_CHANNEL_SHUFFLE)
-        FOCAL_CHECK_ARG(pool->channels[s] >= 1 && pool->channels[s] <= FOCAL_VIEW_MAX_CHANNELS, "view_draw_ex: slot %d has %d channels (1 .. %d)", s, pool->channels[s], FOCAL_VIEW_MAX_CHANNELS);
+        FOCAL_CHECK_ARG(pool->channels[s] >= 1 && pool->channels[s] <= FOCAL_VIEW_MAX_CHANNELS, "view_draw: slot %d has %d channels (1 .. %d)", s, pool->channels[s], FOCAL_VIEW_MAX_CHANNELS);
       if (kd == FOCAL_VIEW_TIME_MASK)
-        FOCAL_CHECK_ARG(pool->tmask_d[s] >= 1 && pool->tmask_i[s] - pool->tmask_d[s] >= 1, "view_draw_ex: time mask of slot %d needs D >= 1 and I - D >= 1 (D = %d, I = %d)", s, pool->tmask_d[s], pool->tmask_i[s]);
+        FOCAL_CHECK_ARG(pool->tmask_d[s] >= 1 && pool->tmask_i[s] - pool->tmask_d[s] >= 1, "view_draw: time mask of slot %d needs D >= 1 and I - D >= 1 (D = %d, I = %d)", s, pool->tmask_d[s], pool->tmask_i[s]);
       if (kd == FOCAL_VIEW_FREQ_MASK)
-        FOCAL_CHECK_ARG(pool->fmask_w[s] >= 2 && pool->fmask_n[s] - pool->fmask_w[s] >= 1, "view_draw_ex: freq mask of slot %d needs W >= 2 and n - W >= 1 (W = %d, n = %d)", s, pool->fmask_w[s], pool->fmask_n[s]);
+        FOCAL_CHECK_ARG(pool->fmask_w[s] >= 2 && pool->fmask_n[s] - pool->fmask_w[s] >= 1, "view_draw: freq mask of slot %d needs W >= 2 and n - W >= 1 (W = %d, n = %d)", s, pool->fmask_w[s], pool->fmask_n[s]);
     }
   }
-  FOCAL_LAUNCH(view_draw_ex_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *pool, n_views, n_slots, state, stream_id, plans, extras, advance ? 1 : 0);
-  FOCAL_LAUNCH_CHECK();
   return FOCAL_OK;
 }
 
-extern "C" int focal_view_draw(const focal_view_pool* pool, int n_views, int n_slots, const uint32_t* seed, uint32_t stream_id,
-                               focal_view_plan* plans, void* stream) {
-  return view_draw_launch(pool, n_views, n_slots, const_cast<uint32_t*>(seed), stream_id, plans, 0, stream);
-}
-
-extern "C" int focal_view_draw_shared(const focal_view_pool* pool, int n_views, int n_slots, uint32_t* view_state, uint32_t stream_id,
-                                      focal_view_plan* plans, void* stream) {
-  FOCAL_CHECK_ARG(view_state != nullptr, "view_draw_shared: null view state (4 words: {seed, draw count, 0, 0})");
-  return view_draw_launch(pool, n_views, n_slots, view_state, stream_id, plans, 1, stream);
+extern "C" int focal_view_draw(const focal_view_pool* pool, int n_views, int n_slots, uint32_t* state, int advance, uint32_t stream_id,
+                               focal_view_plan* plans, focal_view_extra* extras, void* stream) {
+  FOCAL_CHECK_ARG(pool && plans && n_views >= 1 && n_slots >= 1 && n_slots <= FOCAL_VIEW_MAX_SLOTS && n_views * n_slots <= 64,
+                  "view_draw: 1 .. %d slots, at most 64 (view, slot) pairs", FOCAL_VIEW_MAX_SLOTS);
+  FOCAL_CHECK_ARG(!advance || state != nullptr, "view_draw: advance needs the view state (4 words: {seed, draw count, 0, 0})");
+  if (int rc = view_pool_check(pool, n_slots, extras != nullptr)) return rc;
+  if (extras != nullptr)
+    FOCAL_LAUNCH(view_draw_extras_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *pool, n_views, n_slots, state, stream_id, plans, extras, advance ? 1 : 0);
+  else
+    FOCAL_LAUNCH(view_draw_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *pool, n_views, n_slots, state, stream_id, plans, advance ? 1 : 0);
+  FOCAL_LAUNCH_CHECK();
+  return FOCAL_OK;
 }
 
 // The warp curves of focal_amd/warp.py on the device, one workgroup per problem: the not-a-knot cubic spline through the plan's knots

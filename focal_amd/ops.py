@@ -223,7 +223,7 @@ def fft_realpack(x, scale=1.0, flip=False, perm=None, phase=0.0, out=None, **ext
     samples reversed), interval order `perm` (sequence of I ints), and a rotation of every bin by `phase` radians.
     `out`: write into this contiguous [B, 2C, I, n] fp32 tensor (e.g. one half of a two-view batch) instead of allocating.
     jitter=(std, key) / chan=order / time_mask=(lo, n) / freq_mask=(lo, n) / extra=device record / noise_salt=: the augmenters that
-    travel in a focal_view_extra (focal_fft_realpack_multi_ex); without one of them the call is what it always was."""
+    travel in a focal_view_extra (focal_fft_realpack_multi)."""
     if extra:
         return fft_realpack_multi([dict(x=x, scale=scale, flip=flip, perm=perm, phase=phase, out=out, **extra)])[0]
     d, a, x, tw, out = _fft_problem(x, scale, flip, perm, phase, out)
@@ -239,37 +239,30 @@ def fft_realpack_multi(items):
     modalities of a view, or of both views) -> list of outputs.  One call (focal_fft_realpack_multi): the short-row transforms (the
     20-sample sensor modalities) share one launch, the others are launched as fft_realpack would.
     An item may also carry jitter= / chan= / time_mask= / freq_mask= (host values), extra= (a row of new_view_extras: read on the device
-    when the kernel runs) and noise_salt=; a call in which no item does goes to focal_fft_realpack_multi exactly as before, one in which
-    any does goes to focal_fft_realpack_multi_ex."""
-    ex = any(it.get(k) is not None for it in items for k in _EXTRA_KEYS)
+    when the kernel runs) and noise_salt=.  The library, not this function, decides which kernels a call runs: the plain ones unless some
+    item carries an extra."""
     probs = [_fft_problem(**{k: v for k, v in it.items() if k not in _EXTRA_KEYS}) for it in items]
-    arr = ((_lib.FftProblemEx if ex else _lib.FftProblem) * len(probs))()
-    for i, (d, a, x, tw, out) in enumerate(probs):
-        q = arr[i].p if ex else arr[i]
+    arr = (_lib.FftProblem * len(probs))()
+    for q, it, (d, a, x, tw, out) in zip(arr, items, probs):
         q.d = d
         q.has_aug = int(a is not None)
         if a is not None:
             q.aug = a
         q.x, q.twiddle, q.out = _p(x), _p(tw), _p(out)
-        plan = items[i].get("plan")
+        plan = it.get("plan")
         if plan is not None:  # the augmentation is read from the device record when the kernel runs (view draws inside the captured step)
-            _need_cuda(plan, items[i]["x_warped"])
-            q.plan, q.x_warped = _p(plan), _p(items[i]["x_warped"])
-        if ex:
-            it = items[i]
-            arr[i].noise_salt = int(it.get("noise_salt") or 0) & 0xFFFFFFFF
-            if it.get("extra") is not None:
-                rec = it["extra"]
-                _need_cuda(rec)
-                assert rec.dtype == torch.uint8 and rec.numel() == VIEW_EXTRA_BYTES and rec.is_contiguous()
-                arr[i].extra_dev = _p(rec)
-            elif any(it.get(k) is not None for k in ("jitter", "chan", "time_mask", "freq_mask")):
-                arr[i].has_extra = 1
-                arr[i].extra = _host_extra(x, it.get("jitter"), it.get("chan"), it.get("time_mask"), it.get("freq_mask"))
-    if ex:
-        check(_lib.load().focal_fft_realpack_multi_ex(len(probs), arr, _stream()))
-    else:
-        check(_lib.load().focal_fft_realpack_multi(len(probs), arr, _stream()))
+            _need_cuda(plan, it["x_warped"])
+            q.plan, q.x_warped = _p(plan), _p(it["x_warped"])
+        q.noise_salt = int(it.get("noise_salt") or 0) & 0xFFFFFFFF
+        if it.get("extra") is not None:
+            rec = it["extra"]
+            _need_cuda(rec)
+            assert rec.dtype == torch.uint8 and rec.numel() == VIEW_EXTRA_BYTES and rec.is_contiguous()
+            q.extra_dev = _p(rec)
+        elif any(it.get(k) is not None for k in ("jitter", "chan", "time_mask", "freq_mask")):
+            q.has_extra = 1
+            q.extra = _host_extra(x, it.get("jitter"), it.get("chan"), it.get("time_mask"), it.get("freq_mask"))
+    check(_lib.load().focal_fft_realpack_multi(len(probs), arr, _stream()))
     return [p[4] for p in probs]
 
 
@@ -278,38 +271,34 @@ VIEW_KINDS = {"no": _lib.VIEW_NONE, "negation": _lib.VIEW_NEGATION, "scaling": _
               "permutation": _lib.VIEW_PERMUTATION, "phase_shift": _lib.VIEW_PHASE_SHIFT, "mag_warp": _lib.VIEW_MAG_WARP,
               "time_warp": _lib.VIEW_TIME_WARP, "jitter": _lib.VIEW_JITTER, "channel_shuffle": _lib.VIEW_CHANNEL_SHUFFLE,
               "time_mask": _lib.VIEW_TIME_MASK, "freq_mask": _lib.VIEW_FREQ_MASK}
-VIEW_KINDS_EX = ("jitter", "channel_shuffle", "time_mask", "freq_mask")   # the kinds that need focal_view_pool_ex / focal_view_extra
+VIEW_KINDS_EX = ("jitter", "channel_shuffle", "time_mask", "freq_mask")   # the kinds that travel in a focal_view_extra
 VIEW_PLAN_BYTES = C.sizeof(_lib.ViewPlan)
 VIEW_EXTRA_BYTES = C.sizeof(_lib.ViewExtra)
 
 
 def view_pool(entries, intervals, scaling_std=0.2, mag_warp=(0.05, 4), time_warp=(0.2, 6), jitter_std=None, channels=None, time_mask=None,
-              freq_mask=None, extended=False):
-    """entries: [(augmenter name, coin probability)] -- the pool ONE entry of which is drawn per view; intervals: per slot ((location,
-    modality) pair) the interval count a permutation shuffles; the two warps' (magnitude, spline ord).
-    A pool of at most 8 entries of those kinds is a focal_view_pool, as ever.  A longer one (up to 16), or one that names jitter /
-    channel_shuffle / time_mask / freq_mask, is a focal_view_pool_ex with the per-slot lists those need: jitter_std [std], channels
-    [C], time_mask [(D, I)], freq_mask [(W, n)]; extended=True asks for that struct whatever the entries (tests)."""
-    ex = bool(extended) or len(entries) > _lib.VIEW_MAX_POOL or any(name in VIEW_KINDS_EX for name, _ in entries)
-    if not 1 <= len(entries) <= (_lib.VIEW_MAX_POOL_EX if ex else _lib.VIEW_MAX_POOL) or not 1 <= len(intervals) <= _lib.VIEW_MAX_SLOTS:
-        raise ValueError("view_pool: 1 .. 16 pool entries (8 without the extended kinds), 1 .. 8 slots")
-    pool = _lib.ViewPoolEx() if ex else _lib.ViewPool()
-    if ex:
-        names = {name for name, _ in entries}
-        ns = len(intervals)
-        for need, arg, label in (("jitter", jitter_std, "jitter_std"), ("channel_shuffle", channels, "channels"), ("time_mask", time_mask, "time_mask"),
-                                 ("freq_mask", freq_mask, "freq_mask")):
-            if need in names and (arg is None or len(arg) != ns):
-                raise ValueError(f"view_pool: a pool with {need} needs {label}= with one entry per slot")
-        for i in range(ns):
-            if jitter_std is not None:
-                pool.jitter_std[i] = float(jitter_std[i])
-            if channels is not None:
-                pool.channels[i] = int(channels[i])
-            if time_mask is not None:
-                pool.tmask_d[i], pool.tmask_i[i] = int(time_mask[i][0]), int(time_mask[i][1])
-            if freq_mask is not None:
-                pool.fmask_w[i], pool.fmask_n[i] = int(freq_mask[i][0]), int(freq_mask[i][1])
+              freq_mask=None):
+    """entries: [(augmenter name, coin probability)] -- the pool (1 .. 16 entries) ONE entry of which is drawn per view; intervals: per slot
+    ((location, modality) pair) the interval count a permutation shuffles; the two warps' (magnitude, spline ord).  A pool that names
+    jitter / channel_shuffle / time_mask / freq_mask needs that kind's per-slot list: jitter_std [std], channels [C], time_mask [(D, I)],
+    freq_mask [(W, n)]."""
+    if not 1 <= len(entries) <= _lib.VIEW_MAX_POOL or not 1 <= len(intervals) <= _lib.VIEW_MAX_SLOTS:
+        raise ValueError(f"view_pool: 1 .. {_lib.VIEW_MAX_POOL} pool entries, 1 .. {_lib.VIEW_MAX_SLOTS} slots")
+    pool = _lib.ViewPool()
+    names = {name for name, _ in entries}
+    ns = len(intervals)
+    for need, arg, label in zip(VIEW_KINDS_EX, (jitter_std, channels, time_mask, freq_mask), ("jitter_std", "channels", "time_mask", "freq_mask")):
+        if need in names and (arg is None or len(arg) != ns):
+            raise ValueError(f"view_pool: a pool with {need} needs {label}= with one entry per slot")
+    for i in range(ns):
+        if jitter_std is not None:
+            pool.jitter_std[i] = float(jitter_std[i])
+        if channels is not None:
+            pool.channels[i] = int(channels[i])
+        if time_mask is not None:
+            pool.tmask_d[i], pool.tmask_i[i] = int(time_mask[i][0]), int(time_mask[i][1])
+        if freq_mask is not None:
+            pool.fmask_w[i], pool.fmask_n[i] = int(freq_mask[i][0]), int(freq_mask[i][1])
     pool.n_aug = len(entries)
     for i, (name, prob) in enumerate(entries):
         pool.kind[i], pool.prob[i] = VIEW_KINDS[name], float(prob)
@@ -343,37 +332,32 @@ def write_view_extra(extras, index, jitter=None, chan=None, time_mask=None, freq
     extras[index].copy_(torch.frombuffer(bytearray(bytes(e)), dtype=torch.uint8))
 
 
-def _view_draw_ex(pool, n_views, n_slots, state, advance, stream_id, plans, extras):
+def _view_draw(pool, n_views, n_slots, state, advance, stream_id, plans, extras):
+    _need_cuda(plans, state)
+    assert plans.shape == (n_views * n_slots, VIEW_PLAN_BYTES) and plans.dtype == torch.uint8 and plans.is_contiguous()
     if extras is None:
-        raise ValueError("view_draw: an extended pool (ops.view_pool) needs extras=new_view_extras(...)")
-    _need_cuda(extras)
-    assert extras.shape == (n_views * n_slots, VIEW_EXTRA_BYTES) and extras.dtype == torch.uint8 and extras.is_contiguous()
-    check(_lib.load().focal_view_draw_ex(C.byref(pool), n_views, n_slots, _p(state), int(advance), int(stream_id) & 0xFFFFFFFF, _p(plans),
-                                         _p(extras), _stream()))
+        if any(pool.kind[i] >= _lib.VIEW_JITTER for i in range(pool.n_aug)):
+            raise ValueError("view_draw: a pool that names jitter / channel_shuffle / time_mask / freq_mask needs extras=new_view_extras(...)")
+    else:
+        _need_cuda(extras)
+        assert extras.shape == (n_views * n_slots, VIEW_EXTRA_BYTES) and extras.dtype == torch.uint8 and extras.is_contiguous()
+    check(_lib.load().focal_view_draw(C.byref(pool), n_views, n_slots, _p(state), advance, int(stream_id) & 0xFFFFFFFF, _p(plans),
+                                      _p(extras), _stream()))
     return plans
 
 
 def view_draw(pool, n_views, n_slots, seed_state, stream_id, plans, extras=None):
     """The draws of n_views views over n_slots slots into `plans` (new_view_plans), keyed by seed_state[0] (the device seed word the
-    optimizer advances every step) and stream_id.  With an extended pool (view_pool) also into `extras` (new_view_extras)."""
-    _need_cuda(plans, seed_state)
-    assert plans.shape == (n_views * n_slots, VIEW_PLAN_BYTES) and plans.dtype == torch.uint8 and plans.is_contiguous()
-    if isinstance(pool, _lib.ViewPoolEx):
-        return _view_draw_ex(pool, n_views, n_slots, seed_state, 0, stream_id, plans, extras)
-    check(_lib.load().focal_view_draw(C.byref(pool), n_views, n_slots, _p(seed_state), int(stream_id) & 0xFFFFFFFF, _p(plans), _stream()))
-    return plans
+    optimizer advances every step) and stream_id; with extras= (new_view_extras) also the records of jitter / channel_shuffle / time_mask /
+    freq_mask, which a pool that names one of them needs."""
+    return _view_draw(pool, n_views, n_slots, seed_state, 0, stream_id, plans, extras)
 
 
 def view_draw_shared(pool, n_views, n_slots, view_state, stream_id, plans, extras=None):
     """view_draw from the draw's own device state (runtime.view_state: one seed broadcast to every data-parallel rank), which the kernel
     advances itself: every rank draws the same plans, replay after replay."""
-    _need_cuda(plans, view_state)
-    assert plans.shape == (n_views * n_slots, VIEW_PLAN_BYTES) and plans.dtype == torch.uint8 and plans.is_contiguous()
     assert view_state.dtype == torch.int32 and view_state.numel() >= 4
-    if isinstance(pool, _lib.ViewPoolEx):
-        return _view_draw_ex(pool, n_views, n_slots, view_state, 1, stream_id, plans, extras)
-    check(_lib.load().focal_view_draw_shared(C.byref(pool), n_views, n_slots, _p(view_state), int(stream_id) & 0xFFFFFFFF, _p(plans), _stream()))
-    return plans
+    return _view_draw(pool, n_views, n_slots, view_state, 1, stream_id, plans, extras)
 
 
 def read_view_plans(plans):

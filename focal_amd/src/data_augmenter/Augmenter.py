@@ -281,10 +281,10 @@ class Augmenter:
 
     # ------------------------------------------------------------------------------------------ random views, drawn on the device
     def device_draws_supported(self):
-        """The pool is made of augmenters focal_view_draw / focal_view_draw_ex know (every shipped `random_augmenters` pool is)."""
+        """The pool is made of augmenters focal_view_draw knows (every shipped `random_augmenters` pool is)."""
         cfg = self.args.dataset_config
         n_slots = sum(len(cfg["modality_names"]) for _ in cfg["location_names"])
-        return (all(n in ops.VIEW_KINDS for n in self.aug_names) and 1 <= len(self.aug_names) <= ops._lib.VIEW_MAX_POOL_EX
+        return (all(n in ops.VIEW_KINDS for n in self.aug_names) and 1 <= len(self.aug_names) <= ops._lib.VIEW_MAX_POOL
                 and n_slots <= ops._lib.VIEW_MAX_SLOTS)
 
     def _device_state(self, inputs):
@@ -311,8 +311,8 @@ class Augmenter:
         dev = inputs[flat[0][0]][flat[0][1]].device
         n = len(flat)
         warps = any(k in ("mag_warp", "time_warp") for k in self.aug_names)
-        # (an extended pool -- more than 8 entries, or jitter / channel_shuffle / time_mask / freq_mask -- draws an extra record beside each plan)
-        extras = ops.new_view_extras(2, n, dev) if isinstance(pool, ops._lib.ViewPoolEx) else None
+        # (a pool that names jitter / channel_shuffle / time_mask / freq_mask draws an extra record beside each plan)
+        extras = ops.new_view_extras(2, n, dev) if any(k in ops.VIEW_KINDS_EX for k in self.aug_names) else None
         st = {"key": key, "flat": flat, "pool": pool, "plans": ops.new_view_plans(2, n, dev), "extras": extras, "warps": warps,
               "both": {k: torch.empty((2 * inputs[k[0]][k[1]].shape[0], 2 * inputs[k[0]][k[1]].shape[1]) + tuple(inputs[k[0]][k[1]].shape[2:]),
                                       dtype=torch.float32, device=dev) for k in flat},
@@ -339,10 +339,7 @@ class Augmenter:
             stream_id = 0x56494557   # ("VIEW")
         # the draw's own state, started from one seed on every data-parallel rank: identical plans on all ranks (the reference draws once
         # per batch; the global batch is the batch), different dropout masks (runtime.rng_state stays per rank)
-        if st["extras"] is None:
-            ops.view_draw_shared(st["pool"], 2, n, st["view_state"], stream_id, st["plans"])
-        else:
-            ops.view_draw_shared(st["pool"], 2, n, st["view_state"], stream_id, st["plans"], extras=st["extras"])
+        ops.view_draw_shared(st["pool"], 2, n, st["view_state"], stream_id, st["plans"], extras=st["extras"])
         if st["warps"]:
             ops.warp_plan_multi([dict(x=x[l][m], plan=st["plans"][v * n + i], tables=st["tables"][v][(l, m)], y=st["warped"][v][(l, m)])
                                  for v in range(2) for i, (l, m) in enumerate(flat)])

@@ -27,8 +27,8 @@
 extern "C" {
 #endif
 
-/* 7: launch trace (focal_trace_*), focal_adamw_multi_advance takes the step-state length; 2: BatchNorm scratch of 2C + 1 floats; 3: fused MLP, warps, Mixup; 4: row-sharded loss head, weight-gradient launch queries */
-#define FOCAL_ABI_VERSION 13
+/* 14: one view pool (16 entries), one focal_view_draw, one focal_fft_problem that carries the extra; 7: launch trace (focal_trace_*), focal_adamw_multi_advance takes the step-state length; 2: BatchNorm scratch of 2C + 1 floats; 3: fused MLP, warps, Mixup; 4: row-sharded loss head, weight-gradient launch queries */
+#define FOCAL_ABI_VERSION 14
 
 enum { FOCAL_OK = 0, FOCAL_EINVAL = -1, FOCAL_EUNSUPPORTED = -2, FOCAL_EWORKSPACE = -3, FOCAL_EHIP = -4 };
 enum { FOCAL_F32 = 0, FOCAL_BF16 = 1 };
@@ -94,70 +94,22 @@ int focal_fft_realpack_fwd(const focal_fft_desc* d, const float* x, const float*
 typedef struct { float scale; int flip; int use_perm; int perm[FOCAL_AUG_MAX_INTERVALS]; float phase_cos, phase_sin; } focal_aug_desc;
 int focal_augment_fft_fwd(const focal_fft_desc* d, const focal_aug_desc* a, const float* x, const float* twiddle, float* out,
                           void* stream);
-/* n transforms (each with or without an augmentation: the two views x the modalities of a step) in ONE call: problems with short rows
- * (n <= 64 samples as a direct DFT, n2 == 1: the 20-sample sensor modalities) share one launch -- a thread per output bin, 256 / n
- * rows per workgroup pass, a problem table in the kernel arguments, up to 8 problems per launch -- the others are launched as by
- * focal_fft_realpack_fwd / focal_augment_fft_fwd.  Results are those of the single calls. */
 typedef struct focal_view_plan focal_view_plan;
-/* plan (round 5) non-NULL: the augmentation of this transform is read from that DEVICE record when the kernel runs (focal_view_draw
- * fills it inside the same captured step) instead of from `aug`; when the record says the view is warped, rows come from x_warped. */
-typedef struct { focal_fft_desc d; int has_aug; focal_aug_desc aug; const float* x; const float* twiddle; float* out;
-                 const focal_view_plan* plan; const float* x_warped; } focal_fft_problem;
-int focal_fft_realpack_multi(int n, const focal_fft_problem* problems, void* stream);
+/* (focal_fft_realpack_multi, the call the product path makes, is declared behind the view records below: a problem carries one) */
 
-/* ------------------------------------------------------------------------------------------------ view draws on the device (round 5)
+/* ------------------------------------------------------------------------------------------------ views drawn on the device
  * The reference draws a view's augmentation in Python before every forward (data_augmenter/Augmenter.py:76-113 forward_random: ONE
  * augmenter of the pool per call, np.random.randint; each augmenter class then flips its coin per (location, modality), random() < p, and
  * draws its own parameters: ScalingAugmenter.py:35-36 N(1, std), PermutationAugmenter.py:35-36 torch.randperm(intervals),
- * PhaseShiftAugmenter.py:39-54 an angle in (-pi, pi), tsai's random-curve knots N(1, magnitude) for the two warps).  focal_view_draw
- * makes exactly these draws on the device from a counter RNG keyed by (seed word, stream id, view, slot) -- the seed word is the one the
- * optimizer advances every step -- and writes one focal_view_plan per (view, slot); slot = a (location, modality) pair.  Nothing of a
- * random view is left on the host: the draw, the warp tables (focal_warp_plan_fwd) and the transform (focal_fft_realpack_multi with
- * `plan`) are launches of fixed shape, so the whole view generation sits inside the captured step. */
-#define FOCAL_VIEW_MAX_KNOTS 16
-#define FOCAL_VIEW_MAX_POOL 8
-#define FOCAL_VIEW_MAX_SLOTS 8
-enum { FOCAL_VIEW_NONE = 0, FOCAL_VIEW_NEGATION = 1, FOCAL_VIEW_SCALING = 2, FOCAL_VIEW_HFLIP = 3, FOCAL_VIEW_PERMUTATION = 4,
-       FOCAL_VIEW_PHASE_SHIFT = 5, FOCAL_VIEW_MAG_WARP = 6, FOCAL_VIEW_TIME_WARP = 7 };
-struct focal_view_plan {
-  focal_aug_desc aug;                  /* what the transform applies: the identity when the coin flip missed */
-  int kind;                            /* the augmenter drawn for this (view, slot): FOCAL_VIEW_*, 0 = the coin flip missed */
-  int pool_index;                      /* which pool entry the view drew (the same for all its slots) */
-  int warp;                            /* 0, FOCAL_VIEW_MAG_WARP or FOCAL_VIEW_TIME_WARP: the transform reads the warped copy */
-  int nknots;                          /* 3 (ord - 1) + 1 */
-  float knots[FOCAL_VIEW_MAX_KNOTS];   /* the warp's random-curve ordinates */
-};
-typedef struct {
-  int n_aug;                                                   /* pool size: one entry is drawn per view, uniformly */
-  int kind[FOCAL_VIEW_MAX_POOL]; float prob[FOCAL_VIEW_MAX_POOL]; /* FOCAL_VIEW_* and the per-slot coin of each entry */
-  float scaling_std, mag_magnitude, time_magnitude;
-  int mag_order, time_order;                                   /* spline `ord` of the warps (tsai defaults 4 / 6) */
-  int intervals[FOCAL_VIEW_MAX_SLOTS];                         /* per slot: the interval count the permutation shuffles */
-} focal_view_pool;
-/* plans: device [n_views][n_slots].  seed: the device seed word (NULL = 0); stream_id separates this draw from the dropout streams. */
-int focal_view_draw(const focal_view_pool* pool, int n_views, int n_slots, const uint32_t* seed, uint32_t stream_id, focal_view_plan* plans,
-                    void* stream);
-/* The same draws from a state of their own (round 6): view_state = 4 device words {seed, draw count, 0, 0} that the kernel advances after
- * drawing (seed <- mix32(seed + golden), count += 1), so consecutive calls -- consecutive replays of a captured step -- draw different
- * views without any other kernel touching the words.  Under data parallelism every rank holds a copy started from ONE broadcast seed: the
- * ranks then draw identical plans, i.e. the global batch gets one augmenter / coin / permutation / scale / phase per view as the
- * reference's batch does (Augmenter.py:76-113, ScalingAugmenter.py:35 size=(1,), PermutationAugmenter.py:35-36), while the dropout
- * streams (keyed by the word the optimizer advances) stay per-rank. */
-int focal_view_draw_shared(const focal_view_pool* pool, int n_views, int n_slots, uint32_t* view_state, uint32_t stream_id, focal_view_plan* plans,
-                           void* stream);
-/* The warps of up to 8 (view, slot) pairs whose plans may ask for one, as TWO launches (the tables of all of them, then the passes over
- * their windows); a problem whose plan says "no warp" costs nothing and leaves its y unwritten.  Per problem: the random curve through the
- * plan's knots and, for the time warp, its cumulative positions (one workgroup per problem; focal_amd/warp.py is the host statement of the
- * same arithmetic), then x [rows][L] -> y with the 24 resampling weights of focal_warp_fwd's tables formed per position by the pass.  end_coef: device fp32 [47][4][48], the
- * not-a-knot basis splines of a 48-sample end window (focal_amd.warp.end_window_coefficients(), a constant of the method); tables:
- * device workspace of 2 L floats per problem (multipliers, or floor | fraction of the positions), 16-byte aligned. */
-typedef struct { int rows, L; const float* x; const focal_view_plan* plan; float* tables; float* y; } focal_warp_problem;
-int focal_warp_plan_multi(int n, const focal_warp_problem* problems, const float* end_coef, void* stream);
-
-/* ------------------------------------------------------------------------------------------------ jitter / channel shuffle / masks
- * The four remaining view augmenters of the reference's data_augmenter package, as ADDITIONS beside the records above (no existing struct
- * or export changes; the ABI number stays): a focal_view_extra travels beside a focal_view_plan / focal_aug_desc and is the identity
- * when zeroed.
+ * PhaseShiftAugmenter.py:39-54 an angle in (-pi, pi), tsai's random-curve knots N(1, magnitude) for the two warps, ...).  focal_view_draw
+ * makes exactly these draws on the device from a counter RNG keyed by (seed word, stream id, view, slot) and writes one focal_view_plan
+ * and, when asked, one focal_view_extra per (view, slot); slot = a (location, modality) pair.  Nothing of a random view is left on the
+ * host: the draw, the warp tables (focal_warp_plan_multi) and the transform (focal_fft_realpack_multi with `plan` / `extra_dev`) are
+ * launches of fixed shape, so the whole view generation sits inside the captured step.
+ *
+ * Twelve kinds.  0 .. 7 travel in the plan: its focal_aug_desc (negation, scaling, horizontal flip, permutation, phase shift: what
+ * focal_augment_fft_fwd applies) or its warp knots (magnitude warp, time warp).  8 .. 11 travel in the extra record, which is the identity
+ * when zeroed:
  *   time domain   jitter           x' = x + N(0, 1) * std, i.i.d. per element                    JitterAugmenter.py:37-40
  *                 channel shuffle  x'[:, c] = x[:, chan[c]]: one order for the whole batch        ChannelShuffleAugmenter.py:34-37
  *                                  (packed spectrum: output pair (2c, 2c+1) = transform of source channel chan[c])
@@ -173,11 +125,23 @@ int focal_warp_plan_multi(int n, const focal_warp_problem* problems, const float
  *   u1 = 1 - (mix32(k + (2p) * 0x85EBCA6B) >> 8) / 2^24          in (0, 1]
  *   u2 =     (mix32(k + (2p + 1) * 0x85EBCA6B) >> 8) / 2^24      in [0, 1)
  *   z[2p] = sqrt(-2 ln u1) cos(2 pi u2),  z[2p + 1] = sqrt(-2 ln u1) sin(2 pi u2),  x'[e] += jitter_std * z[e]      (fp32)
- * Under data parallelism every rank draws the same key (focal_view_draw_shared); noise_salt = the rank gives the samples of the global
- * batch independent noise, as the reference's one torch.randn over the batch does. */
-#define FOCAL_VIEW_MAX_POOL_EX 16
+ * Under data parallelism every rank draws the same key (focal_view_draw with advance = 1); noise_salt = the rank gives the samples of the
+ * global batch independent noise, as the reference's one torch.randn over the batch does. */
+#define FOCAL_VIEW_MAX_KNOTS 16
+#define FOCAL_VIEW_MAX_POOL 16
+#define FOCAL_VIEW_MAX_SLOTS 8
 #define FOCAL_VIEW_MAX_CHANNELS 16
-enum { FOCAL_VIEW_JITTER = 8, FOCAL_VIEW_CHANNEL_SHUFFLE = 9, FOCAL_VIEW_TIME_MASK = 10, FOCAL_VIEW_FREQ_MASK = 11 };
+enum { FOCAL_VIEW_NONE = 0, FOCAL_VIEW_NEGATION = 1, FOCAL_VIEW_SCALING = 2, FOCAL_VIEW_HFLIP = 3, FOCAL_VIEW_PERMUTATION = 4,
+       FOCAL_VIEW_PHASE_SHIFT = 5, FOCAL_VIEW_MAG_WARP = 6, FOCAL_VIEW_TIME_WARP = 7, FOCAL_VIEW_JITTER = 8,
+       FOCAL_VIEW_CHANNEL_SHUFFLE = 9, FOCAL_VIEW_TIME_MASK = 10, FOCAL_VIEW_FREQ_MASK = 11 };
+struct focal_view_plan {
+  focal_aug_desc aug;                  /* what the transform applies: the identity when the coin flip missed */
+  int kind;                            /* the augmenter drawn for this (view, slot): FOCAL_VIEW_*, 0 = the coin flip missed */
+  int pool_index;                      /* which pool entry the view drew (the same for all its slots) */
+  int warp;                            /* 0, FOCAL_VIEW_MAG_WARP or FOCAL_VIEW_TIME_WARP: the transform reads the warped copy */
+  int nknots;                          /* 3 (ord - 1) + 1 */
+  float knots[FOCAL_VIEW_MAX_KNOTS];   /* the warp's random-curve ordinates */
+};
 typedef struct {
   float jitter_std;                       /* 0 = no noise */
   uint32_t jitter_key;
@@ -185,43 +149,68 @@ typedef struct {
   int tmask_lo, tmask_n;                  /* samples [lo, lo + n) of every row zeroed before the DFT; n = 0: none */
   int fmask_lo, fmask_n;                  /* bins [lo, lo + n) of every output row zeroed; n = 0: none */
 } focal_view_extra;
-/* focal_view_pool with room for the reference's full pool and the per-slot parameters of the four augmenters above */
 typedef struct {
-  int n_aug;
-  int kind[FOCAL_VIEW_MAX_POOL_EX]; float prob[FOCAL_VIEW_MAX_POOL_EX];
+  int n_aug;                                                   /* pool size: one entry is drawn per view, uniformly */
+  int kind[FOCAL_VIEW_MAX_POOL]; float prob[FOCAL_VIEW_MAX_POOL]; /* FOCAL_VIEW_* and the per-slot coin of each entry */
   float scaling_std, mag_magnitude, time_magnitude;
-  int mag_order, time_order;
-  int intervals[FOCAL_VIEW_MAX_SLOTS];
+  int mag_order, time_order;                                   /* spline `ord` of the warps (tsai defaults 4 / 6) */
+  int intervals[FOCAL_VIEW_MAX_SLOTS];                         /* per slot: the interval count the permutation shuffles */
   float jitter_std[FOCAL_VIEW_MAX_SLOTS];  /* value_range[mod] / 100 * std_in_percent */
   int channels[FOCAL_VIEW_MAX_SLOTS];      /* C of the slot's tensor, <= FOCAL_VIEW_MAX_CHANNELS */
   int tmask_d[FOCAL_VIEW_MAX_SLOTS], tmask_i[FOCAL_VIEW_MAX_SLOTS]; /* D = floor(num_segments * mask_ratio); I = x.shape[2] */
   int fmask_w[FOCAL_VIEW_MAX_SLOTS], fmask_n[FOCAL_VIEW_MAX_SLOTS]; /* W = floor(spectrum_len * mask_ratio); n = row length */
-} focal_view_pool_ex;
-/* focal_view_draw (advance = 0: `state` is the seed word, read only) / focal_view_draw_shared (advance = 1: `state` is the 4-word view
- * state, moved on exactly as focal_view_draw_shared moves it) over an extended pool; extras: device [n_views][n_slots] beside plans.
- * For a pool entry of an existing kind the plan bytes are those focal_view_draw writes from the same seed, stream id, view, slot,
- * probabilities and pool position, and the extra is the identity.  The new kinds leave the plan's `aug` the identity and draw from
- * indices of the (view, slot) key no existing kind uses (those use 0 .. 39):
+} focal_view_pool;
+/* plans, extras: device [n_views][n_slots]; stream_id separates this draw from the dropout streams.
+ *   advance = 0: `state` is the device seed word (the one the optimizer advances every step), read only; NULL = 0.
+ *   advance = 1: `state` = 4 device words {seed, draw count, 0, 0} of the draw's own that the kernel advances after drawing
+ *     (seed <- mix32(seed + golden), count += 1), so consecutive calls -- consecutive replays of a captured step -- draw different views
+ *     without any other kernel touching the words.  Under data parallelism every rank holds a copy started from ONE broadcast seed: the
+ *     ranks then draw identical plans, i.e. the global batch gets one augmenter / coin / permutation / scale / phase per view as the
+ *     reference's batch does (Augmenter.py:76-113, ScalingAugmenter.py:35 size=(1,), PermutationAugmenter.py:35-36), while the dropout
+ *     streams (keyed by the word the optimizer advances) stay per-rank.
+ * extras may be NULL: no extra record is written, and a pool that names one of the kinds 8 .. 11 is refused (FOCAL_EINVAL).  The plan
+ * bytes of a draw do not depend on whether extras are written; for a kind 0 .. 7 (and a missed coin) the extra is the identity.  The kinds
+ * 8 .. 11 leave the plan's `aug` the identity and draw from indices of the (view, slot) key no other kind uses (those use 0 .. 39):
  *   jitter           jitter_key = raw draw 40, jitter_std = the slot's
  *   time mask        duration = 1 + floor(u41 * D), start = floor(u42 * (I - duration))     (randint(1, D), torch.randint(0, I - duration))
  *   freq mask        band = 1 + floor(u43 * W), start = floor(u44 * (n - band))
  *   channel shuffle  Fisher-Yates over the slot's C channels, step i (C - 1 .. 1) from draw 48 + i
  * Checked: pool of 1 .. 16; C <= 16; D >= 1 and I - D >= 1; W >= 2 and n - W >= 1 (for the slots in use, when the kind is pooled). */
-int focal_view_draw_ex(const focal_view_pool_ex* pool, int n_views, int n_slots, uint32_t* state, int advance, uint32_t stream_id,
-                       focal_view_plan* plans, focal_view_extra* extras, void* stream);
-/* focal_fft_realpack_multi with an extra per problem: extra_dev non-NULL = a DEVICE record read when the kernel runs (as `plan` is),
- * else the host `extra` when has_extra, else none.  Host extras are checked (C <= 16 and chan a permutation of range(C) when use_chan;
- * mask ranges inside [0, n]; std >= 0); a device record cannot be checked by the host, so the kernel clamps its values
- * (channel entries to [0, C), mask ranges to [0, n], a negative std to 0) and IGNORES use_chan on a tensor of more than 16 channels: the
- * table has no order for them.  focal_view_draw_ex never writes such a record (it refuses a pooled channel shuffle with C > 16); whoever
- * writes records by hand for C > 16 gets jitter and the masks, not the shuffle.  A problem without an extra computes exactly
- * what focal_fft_realpack_multi computes (one workgroup-uniform branch). */
-typedef struct { focal_fft_problem p; int has_extra; focal_view_extra extra; const focal_view_extra* extra_dev; uint32_t noise_salt; } focal_fft_problem_ex;
-int focal_fft_realpack_multi_ex(int n, const focal_fft_problem_ex* problems, void* stream);
+int focal_view_draw(const focal_view_pool* pool, int n_views, int n_slots, uint32_t* state, int advance, uint32_t stream_id,
+                    focal_view_plan* plans, focal_view_extra* extras, void* stream);
+/* The warps of up to 8 (view, slot) pairs whose plans may ask for one, as TWO launches (the tables of all of them, then the passes over
+ * their windows); a problem whose plan says "no warp" costs nothing and leaves its y unwritten.  Per problem: the random curve through the
+ * plan's knots and, for the time warp, its cumulative positions (one workgroup per problem; focal_amd/warp.py is the host statement of the
+ * same arithmetic), then x [rows][L] -> y with the 24 resampling weights of focal_warp_fwd's tables formed per position by the pass.  end_coef: device fp32 [47][4][48], the
+ * not-a-knot basis splines of a 48-sample end window (focal_amd.warp.end_window_coefficients(), a constant of the method); tables:
+ * device workspace of 2 L floats per problem (multipliers, or floor | fraction of the positions), 16-byte aligned. */
+typedef struct { int rows, L; const float* x; const focal_view_plan* plan; float* tables; float* y; } focal_warp_problem;
+int focal_warp_plan_multi(int n, const focal_warp_problem* problems, const float* end_coef, void* stream);
+
+/* n transforms (each with or without an augmentation: the two views x the modalities of a step) in ONE call: problems with short rows
+ * (n <= 64 samples as a direct DFT, n2 == 1: the 20-sample sensor modalities) share one launch -- a thread per output bin, 256 / n
+ * rows per workgroup pass, a problem table in the kernel arguments, up to 8 problems per launch -- the others are launched as by
+ * focal_fft_realpack_fwd / focal_augment_fft_fwd.  Results are those of the single calls.
+ * plan non-NULL: the augmentation of this transform is read from that DEVICE record when the kernel runs (focal_view_draw fills it inside
+ * the same captured step) instead of from `aug`; when the record says the view is warped, rows come from x_warped.
+ * The extra of a problem: extra_dev non-NULL = a DEVICE record read when the kernel runs (as `plan` is), else the host `extra` when
+ * has_extra, else none.  Host extras are checked (C <= 16 and chan a permutation of range(C) when use_chan; mask ranges inside [0, n];
+ * std >= 0); a device record cannot be checked by the host, so the kernel clamps its values (channel entries to [0, C), mask ranges to
+ * [0, n], a negative std to 0) and IGNORES use_chan on a tensor of more than 16 channels: the table has no order for them.
+ * focal_view_draw never writes such a record (it refuses a pooled channel shuffle with C > 16); whoever writes records by hand for C > 16
+ * gets jitter and the masks, not the shuffle.
+ * The library chooses the kernels per call: if some problem has has_extra or a non-NULL extra_dev, every problem of the call runs the
+ * kernels that resolve an extra, where a problem without one (or with the identity) takes one workgroup-uniform branch and computes
+ * exactly what the plain kernels compute; otherwise -- noise_salt alone does not count -- the call runs the plain kernels, which have the
+ * extended code compiled out. */
+typedef struct { focal_fft_desc d; int has_aug; focal_aug_desc aug; const float* x; const float* twiddle; float* out;
+                 const focal_view_plan* plan; const float* x_warped;
+                 int has_extra; focal_view_extra extra; const focal_view_extra* extra_dev; uint32_t noise_salt; } focal_fft_problem;
+int focal_fft_realpack_multi(int n, const focal_fft_problem* problems, void* stream);
 #ifdef __cplusplus
 static_assert(sizeof(focal_view_extra) == 92, "focal_view_extra");
-static_assert(sizeof(focal_view_pool_ex) == 4 + 2 * 64 + 20 + 7 * 32, "focal_view_pool_ex");
-static_assert(sizeof(focal_fft_problem_ex) == sizeof(focal_fft_problem) + 4 + 92 + 8 + 8, "focal_fft_problem_ex");
+static_assert(sizeof(focal_view_pool) == 376, "focal_view_pool");
+static_assert(sizeof(focal_fft_problem) == 328, "focal_fft_problem");
 #endif
 
 /* TimeWarp / MagWarp (data_augmenter/TimeWarpAugmenter.py:18,44, MagWarpAugmenter.py:18,44 -> tsai 0.3.7 TSTimeWarp / TSMagWarp;

@@ -114,10 +114,10 @@ def test_a_stride_that_does_not_divide_the_spectrum_is_refused():
         _net(stride={"audio": 1, "seismic": 2}, spectrum={"seismic": 21})
 
 
-def test_abi_is_13_and_declares_the_new_entry_points():
+def test_abi_number_and_the_ape_stride_entry_points():
     from focal_amd import _lib
     header = open(os.path.join(ROOT, "include", "focal_hip.h")).read()
-    assert re.search(r"#define\s+FOCAL_ABI_VERSION\s+13\b", header) and _lib.ABI_VERSION == 13
+    assert re.search(r"#define\s+FOCAL_ABI_VERSION\s+14\b", header) and _lib.ABI_VERSION == 14
     for name in ("focal_pad_patch_embed_ape_ln_fwd", "focal_pad_patch_embed_ape_ln2_fwd", "focal_ape_bwd", "focal_ape_add_fwd"):
         assert re.search(rf"\bint\s+{name}\s*\(", header), name
         assert name in _lib.PROTOTYPES, name

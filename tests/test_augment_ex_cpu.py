@@ -1,7 +1,7 @@
 """jitter / channel_shuffle / time_mask / freq_mask: the float64 restatement every other test of them measures against, the host draws of
 data_augmenter.Augmenter against the reference classes' (tests/golden/augment_ex_seed5.npz, written by gen_golden_augment_ex.py from the
-reference's JitterAugmenter / ChannelShuffleAugmenter / TimeMaskAugmenter / FreqMaskAugmenter with their draws forced), the ABI additions
-and the constructor's refusals.  Nothing here needs a GPU."""
+reference's JitterAugmenter / ChannelShuffleAugmenter / TimeMaskAugmenter / FreqMaskAugmenter with their draws forced), the folded ABI
+surface and the constructor's refusals.  Nothing here needs a GPU."""
 import copy
 import ctypes as C
 import math
@@ -164,35 +164,56 @@ def test_noise_restatement_is_standard_normal():
     assert not torch.equal(z, restated_noise(0x1234ABCD, 4, (4, 2, 10, 256)).reshape(-1))
 
 
-def test_abi_additions_leave_the_abi_alone():
-    """The new records have the sizes include/focal_hip.h static_asserts; nothing that existed moved; the ABI number stays 13."""
+def test_folded_view_abi_surface():
+    """The folded surface (ABI 14): ONE pool, ONE transform problem and the extra record have the sizes include/focal_hip.h static_asserts,
+    the plan and the augmentation descriptor did not move, and the exports the fold removed are gone."""
     from focal_amd import _lib
     hdr = open(os.path.join(os.path.dirname(_lib._HERE), "include", "focal_hip.h")).read()
     assert re.search(r"static_assert\(sizeof\(focal_view_extra\) == 92,", hdr) and C.sizeof(_lib.ViewExtra) == 92
-    assert re.search(r"static_assert\(sizeof\(focal_view_pool_ex\) == 4 \+ 2 \* 64 \+ 20 \+ 7 \* 32,", hdr) and C.sizeof(_lib.ViewPoolEx) == 376
-    assert re.search(r"sizeof\(focal_fft_problem_ex\) == sizeof\(focal_fft_problem\) \+ 4 \+ 92 \+ 8 \+ 8,", hdr)
-    assert C.sizeof(_lib.FftProblemEx) == C.sizeof(_lib.FftProblem) + 112
-    assert C.sizeof(_lib.AugDesc) == 148 and C.sizeof(_lib.ViewPlan) == 228 and C.sizeof(_lib.ViewPool) == 120 and C.sizeof(_lib.FftProblem) == 216
+    assert re.search(r"static_assert\(sizeof\(focal_view_pool\) == 376,", hdr) and C.sizeof(_lib.ViewPool) == 376
+    assert re.search(r"static_assert\(sizeof\(focal_fft_problem\) == 328,", hdr) and C.sizeof(_lib.FftProblem) == 328
+    assert len(re.findall(r"static_assert\(sizeof\(focal_(?:view|fft)_", hdr)) == 3
+    assert C.sizeof(_lib.AugDesc) == 148 and C.sizeof(_lib.ViewPlan) == 228
+    assert re.search(r"#define FOCAL_VIEW_MAX_POOL 16\b", hdr) and _lib.VIEW_MAX_POOL == 16
     assert (_lib.VIEW_JITTER, _lib.VIEW_CHANNEL_SHUFFLE, _lib.VIEW_TIME_MASK, _lib.VIEW_FREQ_MASK) == (8, 9, 10, 11)
-    assert "#define FOCAL_ABI_VERSION 13" in hdr and _lib.ABI_VERSION == 13
+    assert re.search(r"FOCAL_VIEW_JITTER = 8,\s+FOCAL_VIEW_CHANNEL_SHUFFLE = 9, FOCAL_VIEW_TIME_MASK = 10, FOCAL_VIEW_FREQ_MASK = 11", hdr)
+    assert "#define FOCAL_ABI_VERSION 14" in hdr and _lib.ABI_VERSION == 14
+    gone = ("focal_view_draw_ex", "focal_view_draw_shared", "focal_fft_realpack_multi_ex")
+    assert not any(re.search(name + r"\b", hdr) for name in gone + ("focal_view_pool_ex", "focal_fft_problem_ex", "FOCAL_VIEW_MAX_POOL_EX"))
+    assert not any(name in _lib.PROTOTYPES for name in gone) and not any(hasattr(_lib, n) for n in ("ViewPoolEx", "FftProblemEx", "VIEW_MAX_POOL_EX"))
     if os.path.exists(_lib.LIB_PATH):
         lib = _lib.load()
-        assert lib.focal_abi_version() == 13
-        assert hasattr(lib, "focal_view_draw_ex") and hasattr(lib, "focal_fft_realpack_multi_ex")
+        assert lib.focal_abi_version() == 14
+        assert not any(hasattr(lib, name) for name in gone)
+        assert hasattr(lib, "focal_view_draw") and hasattr(lib, "focal_fft_realpack_multi")
 
 
-def test_view_pool_keeps_the_old_struct_for_old_pools():
+def test_view_pool_fills_one_struct_and_refuses_bad_pools(cfg):
+    """What view_pool fills and refuses; a pool of 9 .. 16 entries of the kinds 0 .. 7 is accepted and the Augmenter allocates no extras
+    for it."""
     from focal_amd import _lib, ops
     old = ops.view_pool([("permutation", 0.5), ("scaling", 0.5)], [10, 10])
-    assert type(old) is _lib.ViewPool
+    assert old.n_aug == 2 and old.kind[0] == 4 and old.kind[1] == 2 and old.intervals[1] == 10
     new = ops.view_pool([("permutation", 0.5), ("jitter", 0.5), ("time_mask", 0.5)], [10, 10], jitter_std=[0.1, 0.2], time_mask=[(3, 10), (3, 10)])
-    assert type(new) is _lib.ViewPoolEx and new.kind[1] == 8 and abs(new.jitter_std[1] - 0.2) < 1e-7 and new.tmask_d[0] == 3 and new.tmask_i[1] == 10
-    assert type(ops.view_pool([("negation", 0.5)] * 9, [10])) is _lib.ViewPoolEx    # more than 8 entries of old kinds
+    assert new.kind[1] == 8 and abs(new.jitter_std[1] - 0.2) < 1e-7 and new.tmask_d[0] == 3 and new.tmask_i[1] == 10
+    assert type(old) is type(new) is _lib.ViewPool
+    nine = ops.view_pool([("negation", 0.5)] * 9, [10])                               # more than 8 entries of old kinds
+    assert nine.n_aug == 9 and all(nine.kind[i] == 1 for i in range(9))
+    assert ops.view_pool([("negation", 0.5)] * 16, [10]).n_aug == 16
     with pytest.raises(ValueError):
         ops.view_pool([("negation", 0.5)] * 17, [10])
     with pytest.raises(ValueError):
         ops.view_pool([("jitter", 0.5)], [10, 10])                                    # jitter without its per-slot std
     assert set(ops.VIEW_KINDS) >= {"jitter", "channel_shuffle", "time_mask", "freq_mask"}
+    # the Augmenter decides on the NAMES: nine old-kind entries draw no extras (the state's tensors follow the inputs: CPU ones here)
+    from data_augmenter import Augmenter as A
+    x = {"shake": {m: torch.zeros(2, 1, 10, 20) for m in MODS}}
+    nine = A.Augmenter(args_with_pool(cfg, ["negation", "scaling", "horizontal_flip"] * 3, []))
+    st = nine._device_state(x)
+    assert nine.device_draws_supported() and st["pool"].n_aug == 9 and st["extras"] is None and st["plans"].shape == (4, 228)
+    four = A.Augmenter(args_with_pool(cfg, ["negation", "time_mask"], []))
+    st = four._device_state(x)
+    assert st["pool"].n_aug == 2 and st["extras"] is not None and st["extras"].shape == (4, 92)
 
 
 def test_augmenter_accepts_a_pool_naming_all_four(cfg):

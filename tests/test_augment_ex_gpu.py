@@ -128,15 +128,15 @@ def test_bad_extras_are_refused(ops):
         with pytest.raises(ValueError):
             ops.fft_realpack(x, **kw)
     from focal_amd import _lib
-    arr = (_lib.FftProblemEx * 1)()
+    arr = (_lib.FftProblem * 1)()
     d, a, xx, tw, out = ops._fft_problem(x)
-    arr[0].p.d, arr[0].p.x, arr[0].p.twiddle, arr[0].p.out = d, x.data_ptr(), tw.data_ptr(), out.data_ptr()
+    arr[0].d, arr[0].x, arr[0].twiddle, arr[0].out = d, x.data_ptr(), tw.data_ptr(), out.data_ptr()
     arr[0].has_extra = 1
     for field, val in (("tmask_n", 21), ("fmask_lo", 21), ("use_chan", 1)):   # (use_chan with chan = 0, 0, 0: not a permutation)
         e = _lib.ViewExtra()
         setattr(e, field, val)
         arr[0].extra = e
-        assert _lib.load().focal_fft_realpack_multi_ex(1, arr, None) == -1 and b"fft_realpack_multi_ex" in _lib.load().focal_last_error()
+        assert _lib.load().focal_fft_realpack_multi(1, arr, None) == -1 and b"fft_realpack_multi:" in _lib.load().focal_last_error()
     for kw in (dict(time_mask=[(0, 10)] * 2), dict(time_mask=[(3, 3)] * 2), dict(freq_mask=[(1, 20)] * 2), dict(freq_mask=[(20, 20)] * 2),
                dict(channels=[17, 3])):
         name = "channel_shuffle" if "channels" in kw else next(iter(kw))
@@ -199,7 +199,7 @@ def sigma45(p, m):
 
 
 def test_extended_draws_have_the_reference_distributions(ops):
-    """(new ground) focal_view_draw_ex, the reference's full eleven-entry pool, 8 views x 8 slots x 200 seed words = 12 800 records and
+    """(new ground) focal_view_draw with extras, the reference's full eleven-entry pool, 8 views x 8 slots x 200 seed words = 12 800 records and
     1 600 pool draws.  Every bound is 4.5 sigma of the binomial for the number of samples at hand."""
     from focal_amd import _lib
     names = ALL_TIME + ALL_FREQ
@@ -208,7 +208,7 @@ def test_extended_draws_have_the_reference_distributions(ops):
     stds = [0.05 * (s + 1) for s in range(n_slots)]
     fm = [(6, 20)] * 6 + [(480, 1600)] * 2
     pool = ops.view_pool([(n, 0.5) for n in names], [10] * n_slots, jitter_std=stds, channels=chans, time_mask=[(3, 10)] * n_slots, freq_mask=fm)
-    assert type(pool) is _lib.ViewPoolEx
+    assert type(pool) is _lib.ViewPool and pool.n_aug == 11
     per = n_views * n_slots
     plans, extras = ops.new_view_plans(S * n_views, n_slots, DEV), ops.new_view_extras(S * n_views, n_slots, DEV)
     seed = ops.new_rng_state(1, DEV)
@@ -290,12 +290,9 @@ def test_extended_draws_have_the_reference_distributions(ops):
 
 # ---------------------------------------------------------------------------------------------- 4. compatibility
 def test_extended_draw_writes_the_old_kinds_bytes(ops):
-    """focal_view_draw_ex over a pool of today's kinds: plan bytes equal focal_view_draw's (and the shared form's, state words included),
-    extras all identity -- 50 seeds."""
-    from focal_amd import _lib
-    old = ops.view_pool(FOCAL_POOL, [10, 10])
-    new = ops.view_pool(FOCAL_POOL, [10, 10], extended=True)
-    assert type(old) is _lib.ViewPool and type(new) is _lib.ViewPoolEx
+    """The draw with extras= over a pool of the kinds 0 .. 7 (ONE pool, both ways): plan bytes equal those of the draw without extras (and
+    the advancing form's, state words included), extras all identity -- 50 seeds."""
+    old = new = ops.view_pool(FOCAL_POOL, [10, 10])
     seed = ops.new_rng_state(1, DEV)
     pa, pb, eb = ops.new_view_plans(2, 2, DEV), ops.new_view_plans(2, 2, DEV), ops.new_view_extras(2, 2, DEV)
     for i in range(50):
@@ -315,7 +312,7 @@ def test_extended_draw_writes_the_old_kinds_bytes(ops):
 
 @pytest.mark.parametrize("shape", SHAPES + [(2, 1, 10, 1600)])
 def test_identity_extras_change_no_bit(ops, shape):
-    """focal_fft_realpack_multi_ex with identity extras (none, a zero host record, a zero device record) against focal_fft_realpack_multi:
+    """focal_fft_realpack_multi with identity extras (none, a zero host record, a zero device record) against the call without any:
     the plan path and the host-augmentation path."""
     x = rnd(*shape, seed=3)
     I = shape[2]
@@ -325,6 +322,11 @@ def test_identity_extras_change_no_bit(ops, shape):
     ops.write_view_plan(plans, 0, **aug)
     plain_host = ops.fft_realpack_multi([dict(x=x, **aug), dict(x=x)])
     plain_plan = ops.fft_realpack_multi([dict(x=x, plan=plans[0], x_warped=x)])
+    # problems WITHOUT an extra inside a call that runs the extended kernels (another problem of the call carries one, on the host or on the device)
+    for carrier in (dict(x=x, time_mask=(1, 2)), dict(x=x, extra=zero[0])):
+        got = ops.fft_realpack_multi([carrier, dict(x=x, **aug), dict(x=x), dict(x=x, plan=plans[0], x_warped=x), dict(x=x, noise_salt=5)])
+        assert torch.equal(got[1], plain_host[0]) and torch.equal(got[2], plain_host[1]) and torch.equal(got[3], plain_plan[0]), carrier
+        assert torch.equal(got[4], plain_host[1]), carrier
     for extra_kw in (dict(noise_salt=0), dict(noise_salt=5, time_mask=(0, 0)), dict(extra=zero[0])):
         got = ops.fft_realpack_multi([dict(x=x, **aug, **extra_kw), dict(x=x, **extra_kw)])
         assert torch.equal(got[0], plain_host[0]) and torch.equal(got[1], plain_host[1]), extra_kw
@@ -362,7 +364,7 @@ def view_reference(x, p, e, salt=0):
 def test_product_pair_with_the_full_pool_follows_the_restatement(ops, cfg):
     """Augmenter.forward_random_pair on the reference's eleven-augmenter pool: whatever the device drew, each view is the restatement's view
     for the drawn records; over 64 seeds all eleven augmenters and the identity occur."""
-    from focal_amd import _lib, runtime
+    from focal_amd import runtime
     aug = product_augmenter(cfg)
     assert aug.device_draws_supported()
     tx = {"shake": {"audio": rnd(2, 1, 10, 1600, seed=1), "seismic": rnd(2, 1, 10, 20, seed=2)}}
@@ -375,7 +377,7 @@ def test_product_pair_with_the_full_pool_follows_the_restatement(ops, cfg):
             seed[0] = 1000 + 17 * it
             v = aug.forward_random_pair(tx)
             st = next(iter(aug._dev_states.values()))
-            assert [k[1] for k in st["flat"]] == mods and type(st["pool"]) is _lib.ViewPoolEx and len(aug._dev_states) == 1
+            assert [k[1] for k in st["flat"]] == mods and st["extras"] is not None and len(aug._dev_states) == 1
             plans, extras = ops.read_view_plans(st["plans"]), ops.read_view_extras(st["extras"])
             for view in range(2):
                 for i, m in enumerate(mods):
@@ -430,7 +432,7 @@ def test_captured_pair_draws_fresh_jitter_on_every_replay(ops, cfg):
 
 @pytest.mark.parametrize("name", ["jitter", "channel_shuffle", "time_mask", "freq_mask"])
 def test_host_path_forward_random_with_forced_draws(ops, cfg, monkeypatch, name):
-    """Augmenter.forward("random") end to end -- host draws (forced), keywords, focal_fft_realpack_multi_ex -- with a one-entry pool of each
+    """Augmenter.forward("random") end to end -- host draws (forced), keywords, focal_fft_realpack_multi -- with a one-entry pool of each
     new kind, against the restatement.  The seismic rows are 8 samples long, so the forced time mask [6, 9) is clipped to [6, 8) there."""
     from data_augmenter import Augmenter as A
     aug = product_augmenter(cfg, [name] if name != "freq_mask" else [], [name] if name == "freq_mask" else [])

@@ -137,11 +137,11 @@ def test_mean_fusion_block_is_a_container_that_points_to_the_engine(net3):
         blk(torch.zeros(1, 2, 3, 3))
 
 
-def test_abi_is_13_and_declares_the_new_entry_points():
+def test_abi_number_and_the_multiloc_entry_points():
     import ctypes as C
     from focal_amd import _lib
     header = open(os.path.join(ROOT, "include", "focal_hip.h")).read()
-    assert re.search(r"#define\s+FOCAL_ABI_VERSION\s+13\b", header) and _lib.ABI_VERSION == 13
+    assert re.search(r"#define\s+FOCAL_ABI_VERSION\s+14\b", header) and _lib.ABI_VERSION == 14
     for name in ("focal_conv_in_bwd_data", "focal_rows_mean"):
         assert re.search(rf"\bint\s+{name}\s*\(", header), name
         assert name in _lib.PROTOTYPES, name

@@ -79,7 +79,7 @@ def test_bench_launches_its_own_ranks():
 
 def test_two_ranks_draw_the_same_views():
     """VERDICT r5 item 3a on the device: both ranks of a job draw identical focal_view_plan records step after step (one broadcast draw
-    seed, focal_view_draw_shared), and different dropout masks (tests/dp_views_worker.py)."""
+    seed, focal_view_draw with advance = 1), and different dropout masks (tests/dp_views_worker.py)."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="8")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(HERE, "dp_views_worker.py")]

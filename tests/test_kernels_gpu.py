@@ -1415,7 +1415,7 @@ def test_product_augmenter_device_pair_follows_the_oracle(ops, cfg):
 
 
 def test_shared_view_draws_advance_their_own_state(ops):
-    """focal_view_draw_shared (round 6): the draw reads its OWN 4-word state and moves it on (seed <- mix32(seed + golden), count += 1):
+    """focal_view_draw with advance = 1 (ops.view_draw_shared): the draw reads its OWN 4-word state and moves it on (seed <- mix32(seed + golden), count += 1):
     two states started from one seed -- two data-parallel ranks -- draw identical plan sequences, consecutive calls differ, and call k
     equals focal_view_draw on the k-th word of the sequence."""
     pool = ops.view_pool(FOCAL_POOL, [10, 10])

@@ -61,7 +61,8 @@ def main():
         ops.fft_realpack(torch.randn_like(x) * std + x, out=out)
 
     variants = {"plain": lambda: ops.fft_realpack(x, out=out),
-                "plain through the _ex export (identity extra)": lambda: ops.fft_realpack(x, out=out, noise_salt=0),
+                "plain through the multi export (noise_salt only: the plain kernels)": lambda: ops.fft_realpack(x, out=out, noise_salt=0),
+                "identity extra (the extended kernels' plain branch)": lambda: ops.fft_realpack(x, out=out, time_mask=(0, 0)),
                 "jitter folded": lambda: ops.fft_realpack(x, out=out, jitter=(std, 12345)),
                 "jitter two-pass (randn_like * s + x, then plain)": two_pass,
                 "channel_shuffle": lambda: ops.fft_realpack(x, out=out, chan=[0]),
