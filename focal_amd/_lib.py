@@ -62,6 +62,18 @@ class FftProblem(C.Structure):
                 ("noise_salt", C.c_uint32)]
 
 
+MIX_MAX_BATCH, MIX_GAMMA_TRIES = 4096, 16
+
+
+class MixRecord(C.Structure):
+    """What focal_mixup_draw drew (include/focal_hip.h: focal_mix_record): box[slot] = yl, yh, xl, xh; apply = 0 is the identity."""
+    _fields_ = [("apply", C.c_int), ("cut", C.c_int), ("lam", C.c_float), ("box", (C.c_int * 4) * VIEW_MAX_SLOTS)]
+
+
+class MixProblem(C.Structure):
+    _fields_ = [("B", C.c_int), ("C", C.c_int), ("I", C.c_int), ("S", C.c_int), ("x", C.c_void_p), ("y", C.c_void_p), ("slot", C.c_int)]
+
+
 class WarpProblem(C.Structure):
     _fields_ = [("rows", C.c_int), ("L", C.c_int), ("x", C.c_void_p), ("plan", C.c_void_p), ("tables", C.c_void_p), ("y", C.c_void_p)]
 
@@ -162,6 +174,9 @@ PROTOTYPES = {
     "focal_view_draw": (C.c_int, [C.POINTER(ViewPool), C.c_int, C.c_int, P, C.c_int, C.c_uint32, P, P, P]),
     "focal_warp_plan_multi": (C.c_int, [C.c_int, C.POINTER(WarpProblem), P, P]),
     "focal_mixup_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P]),
+    "focal_mixup_draw": (C.c_int, [C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), P, C.c_int,
+                                   C.c_uint32, P, P, P]),
+    "focal_mixup_multi": (C.c_int, [C.c_int, C.POINTER(MixProblem), P, P, P]),
     "focal_pad_patch_embed_ln_fwd": (C.c_int, [C.POINTER(EmbedDesc), P, P, P, P, P, P, P]),
     "focal_pad_patch_embed_ln2_fwd": (C.c_int, [C.POINTER(EmbedDesc), P, P, P, P, P, P, P, P, C.c_float, C.c_int, P, P, P]),
     "focal_pad_patch_embed_ape_ln_fwd": (C.c_int, [C.POINTER(Embed2Desc), P, P, P, P, P, P, P, P]),

@@ -470,3 +470,199 @@ extern "C" int focal_mixup_fwd(int B, int C_, int I, int S, const float* x, cons
   FOCAL_LAUNCH_CHECK();
   return FOCAL_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ Mixup drawn on the device
+// The draws of one Mixup call (include/focal_hip.h: focal_mixup_draw states every index and formula), one workgroup: thread 0 makes the
+// scalar draws while everybody hashes the samples; the permutation is the rank of each sample's hash among all of them (LDS-resident,
+// every lane reads the same word per step: a broadcast), not a serial Fisher-Yates over B.
+constexpr int MD_THREADS = 1024;
+struct MixDrawCfg { float prob, switch_prob, mixup_alpha, cutmix_alpha; int B, n_slots; int I[FOCAL_VIEW_MAX_SLOTS], S[FOCAL_VIEW_MAX_SLOTS]; };
+
+// Gamma(alpha) by Marsaglia-Tsang from the draws of stream g; < 0 when the tries ran out
+__device__ float md_gamma(uint32_t km, int g, float alpha) {
+  const float a = alpha < 1.0f ? alpha + 1.0f : alpha;
+  const float d = a - 1.0f / 3.0f, c = 1.0f / sqrtf(9.0f * d);
+  for (int t = 0; t < FOCAL_MIX_GAMMA_TRIES; ++t) {
+    const float x = vd_normal(km, 32 + 16 * g + t);
+    float v = 1.0f + c * x;
+    v = v * v * v;
+    const float w = 1.0f - vd_uniform(km, 128 + 16 * g + t);
+    if (v > 0.0f && logf(w) < 0.5f * x * x + d - d * v + d * logf(v)) {
+      float gm = d * v;
+      if (alpha < 1.0f) gm *= powf(1.0f - vd_uniform(km, 4 + g), 1.0f / alpha);
+      return gm;
+    }
+  }
+  return -1.0f;
+}
+
+__global__ __launch_bounds__(MD_THREADS) void mixup_draw_kernel(const MixDrawCfg cfg, uint32_t* state, uint32_t stream_id,
+                                                                focal_mix_record* __restrict__ rec, int* __restrict__ perm, int advance) {
+  __shared__ uint32_t s_hash[FOCAL_MIX_MAX_BATCH];
+  const int t = threadIdx.x, B = cfg.B;
+  const uint32_t s0 = state ? state[0] : 0u;
+  if (advance) {
+    __syncthreads();  // everybody has read the seed word
+    if (t == 0) {
+      state[0] = focal_mix32(s0 + 0x9E3779B9U);
+      state[1] += 1u;
+    }
+  }
+  const uint32_t km = focal_mix32(s0 * 0x9E3779B9U + stream_id * 0x85EBCA6BU + 0x4D495855U);
+  const uint32_t kp = focal_mix32(km ^ 0x5045524DU);
+  for (int b = t; b < B; b += MD_THREADS) s_hash[b] = focal_mix32(kp + (uint32_t)b * 0x85EBCA6BU);
+  if (t == 0) {
+    const int apply = vd_uniform(km, 0) < cfg.prob ? 1 : 0;
+    int cut = 0;
+    float lam = 1.0f;
+    if (apply) {
+      const bool both = cfg.mixup_alpha > 0.0f && cfg.cutmix_alpha > 0.0f;
+      cut = both ? (vd_uniform(km, 1) < cfg.switch_prob ? 1 : 0) : (cfg.cutmix_alpha > 0.0f ? 1 : 0);
+      const float alpha = cut ? cfg.cutmix_alpha : cfg.mixup_alpha;
+      if (alpha == 1.0f) {
+        lam = vd_uniform(km, 2);
+      } else {
+        const float g0 = md_gamma(km, 0, alpha), g1 = md_gamma(km, 1, alpha);
+        lam = (g0 >= 0.0f && g1 >= 0.0f) ? g0 / (g0 + g1) : 0.5f;
+        if (!(lam >= 0.0f && lam <= 1.0f)) lam = 0.5f;  // 0 / 0 (both draws underflowed), NaN
+      }
+    }
+    rec->apply = apply; rec->cut = cut; rec->lam = lam;
+    const float ratio = sqrtf(1.0f - lam);
+    for (int q = 0; q < FOCAL_VIEW_MAX_SLOTS; ++q) {
+      int yl = 0, yh = 0, xl = 0, xh = 0;
+      if (apply && cut && q < cfg.n_slots) {
+        const int I = cfg.I[q], S = cfg.S[q];
+        const int cut_h = (int)((float)I * ratio), cut_w = (int)((float)S * ratio);
+        int cy = (int)(vd_uniform(km, 8 + 2 * q) * (float)I), cx = (int)(vd_uniform(km, 9 + 2 * q) * (float)S);
+        cy = cy < I ? cy : I - 1;
+        cx = cx < S ? cx : S - 1;
+        yl = min(max(cy - cut_h / 2, 0), I); yh = min(max(cy + cut_h / 2, 0), I);
+        xl = min(max(cx - cut_w / 2, 0), S); xh = min(max(cx + cut_w / 2, 0), S);
+      }
+      rec->box[q][0] = yl; rec->box[q][1] = yh; rec->box[q][2] = xl; rec->box[q][3] = xh;
+    }
+  }
+  __syncthreads();
+  for (int b = t; b < B; b += MD_THREADS) {
+    const uint32_t h = s_hash[b];
+    int rank = 0;
+    for (int j = 0; j < B; ++j) {
+      const uint32_t hj = s_hash[j];
+      rank += (hj < h || (hj == h && j < b)) ? 1 : 0;
+    }
+    perm[b] = rank;
+  }
+}
+
+extern "C" int focal_mixup_draw(float prob, float switch_prob, float mixup_alpha, float cutmix_alpha, int B, int n_slots, const int* I,
+                                const int* S, uint32_t* state, int advance, uint32_t stream_id, focal_mix_record* rec, int* perm,
+                                void* stream) {
+  FOCAL_CHECK_ARG(rec && perm && I && S, "mixup_draw: the record, the permutation and the slot shapes are needed");
+  FOCAL_CHECK_ARG(prob >= 0.f && prob <= 1.f && switch_prob >= 0.f && switch_prob <= 1.f, "mixup_draw: prob and switch_prob lie in [0, 1]");
+  FOCAL_CHECK_ARG(mixup_alpha >= 0.f && cutmix_alpha >= 0.f && (mixup_alpha > 0.f || cutmix_alpha > 0.f),
+                  "mixup_draw: one of mixup_alpha > 0, cutmix_alpha > 0 should be true (neither negative)");
+  FOCAL_CHECK_ARG(B >= 1 && B <= FOCAL_MIX_MAX_BATCH, "mixup_draw: batch %d outside 1 .. %d", B, FOCAL_MIX_MAX_BATCH);
+  FOCAL_CHECK_ARG(n_slots >= 1 && n_slots <= FOCAL_VIEW_MAX_SLOTS, "mixup_draw: %d slots outside 1 .. %d", n_slots, FOCAL_VIEW_MAX_SLOTS);
+  FOCAL_CHECK_ARG(!advance || state != nullptr, "mixup_draw: advance needs the draw state (4 words: {seed, draw count, 0, 0})");
+  MixDrawCfg cfg;
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.prob = prob; cfg.switch_prob = switch_prob; cfg.mixup_alpha = mixup_alpha; cfg.cutmix_alpha = cutmix_alpha;
+  cfg.B = B; cfg.n_slots = n_slots;
+  for (int q = 0; q < n_slots; ++q) {
+    FOCAL_CHECK_ARG(I[q] >= 1 && S[q] >= 1, "mixup_draw: slot %d is %d x %d (both at least 1)", q, I[q], S[q]);
+    cfg.I[q] = I[q]; cfg.S[q] = S[q];
+  }
+  FOCAL_LAUNCH(mixup_draw_kernel, dim3(1), dim3(MD_THREADS), 0, (hipStream_t)stream, cfg, state, stream_id, rec, perm, advance ? 1 : 0);
+  FOCAL_LAUNCH_CHECK();
+  return FOCAL_OK;
+}
+
+// The mix pass of every slot of a step, one launch: blockIdx.z = problem, blockIdx.y = sample, blockIdx.x strides over the sample's
+// C*I*S values (focal_mixup_fwd divides the flat index by the sample size per element; here the grid carries the sample).  VEC: four
+// values per thread through 16-byte accesses; the (interval, sample) coordinates of the box test step along with the four values.
+struct MixTable { int n; int vec[FOCAL_VIEW_MAX_SLOTS]; focal_mix_problem p[FOCAL_VIEW_MAX_SLOTS]; };
+
+__device__ __forceinline__ float mix_one(float a, float o, float lam, int cut, bool inside) {
+  if (cut) return inside ? o : a;
+  // focal_mixup_fwd's `lam * a + (1 - lam) * o`, with the contraction spelled out.  Left to the compiler, mixup_kernel itself rounds in two
+  // ways: its unrolled loop (threads with two or more elements: the training batch) as one product and one fused multiply-add, this form;
+  // its remainder loop (small tensors) as two products and an add.  The same happened to the two paths here.  Pinned, both paths round
+  // alike at every size; against mixup_kernel's unfused loop the result differs by at most one ulp of max(|a|, |o|).
+  return fmaf(lam, a, (1.0f - lam) * o);
+}
+
+__global__ __launch_bounds__(256) void mixup_multi_kernel(const MixTable tab, const focal_mix_record* __restrict__ rec,
+                                                          const int* __restrict__ perm) {
+  const focal_mix_problem& P = tab.p[blockIdx.z];
+  const int b = blockIdx.y;
+  if (b >= P.B) return;
+  const int I = P.I, S = P.S;
+  const int per = P.C * I * S;  // < 2^31: checked by the launcher
+  const float* __restrict__ xa = P.x + (long)b * per;
+  float* __restrict__ yo = P.y + (long)b * per;
+  const int apply = rec->apply;
+  if (!apply) {  // the identity: y = x
+    if (tab.vec[blockIdx.z]) {
+      for (int e = (blockIdx.x * 256 + threadIdx.x) * 4; e < per; e += gridDim.x * 1024)
+        *reinterpret_cast<float4*>(yo + e) = *reinterpret_cast<const float4*>(xa + e);
+    } else {
+      for (int e = blockIdx.x * 256 + threadIdx.x; e < per; e += gridDim.x * 256) yo[e] = xa[e];
+    }
+    return;
+  }
+  // what a device record says is clamped before it moves a read
+  const int pb = min(max(perm[b], 0), P.B - 1);
+  const float* __restrict__ xo = P.x + (long)pb * per;
+  const float lam = rec->lam;
+  const int cut = rec->cut;
+  const int yl = min(max(rec->box[P.slot][0], 0), I), yh = min(max(rec->box[P.slot][1], 0), I);
+  const int xl = min(max(rec->box[P.slot][2], 0), S), xh = min(max(rec->box[P.slot][3], 0), S);
+  if (tab.vec[blockIdx.z]) {
+    for (int e = (blockIdx.x * 256 + threadIdx.x) * 4; e < per; e += gridDim.x * 1024) {
+      const float4 a = *reinterpret_cast<const float4*>(xa + e);
+      const float4 o = *reinterpret_cast<const float4*>(xo + e);
+      int s = e % S, i = (e / S) % I;
+      bool in[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        in[k] = i >= yl && i < yh && s >= xl && s < xh;
+        if (++s == S) { s = 0; if (++i == I) i = 0; }
+      }
+      *reinterpret_cast<float4*>(yo + e) = make_float4(mix_one(a.x, o.x, lam, cut, in[0]), mix_one(a.y, o.y, lam, cut, in[1]),
+                                                       mix_one(a.z, o.z, lam, cut, in[2]), mix_one(a.w, o.w, lam, cut, in[3]));
+    }
+  } else {
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < per; e += gridDim.x * 256) {
+      const int s = e % S, i = (e / S) % I;
+      yo[e] = mix_one(xa[e], xo[e], lam, cut, i >= yl && i < yh && s >= xl && s < xh);
+    }
+  }
+}
+
+extern "C" int focal_mixup_multi(int n, const focal_mix_problem* problems, const focal_mix_record* rec, const int* perm, void* stream) {
+  FOCAL_CHECK_ARG(n >= 1 && n <= FOCAL_VIEW_MAX_SLOTS && problems && rec && perm, "mixup_multi: 1 .. %d problems, a record and a permutation",
+                  FOCAL_VIEW_MAX_SLOTS);
+  MixTable tab;
+  memset(&tab, 0, sizeof(tab));
+  tab.n = n;
+  long max_items = 1;
+  for (int k = 0; k < n; ++k) {
+    const focal_mix_problem& q = problems[k];
+    FOCAL_CHECK_ARG(q.B >= 1 && q.B <= FOCAL_MIX_MAX_BATCH && q.C >= 1 && q.I >= 1 && q.S >= 1 && q.x && q.y && q.x != q.y,
+                    "mixup_multi: bad problem %d (in-place is not supported)", k);
+    FOCAL_CHECK_ARG(q.B == problems[0].B, "mixup_multi: problem %d has batch %d, the permutation is one of %d samples", k, q.B, problems[0].B);
+    FOCAL_CHECK_ARG(q.slot >= 0 && q.slot < FOCAL_VIEW_MAX_SLOTS, "mixup_multi: problem %d names slot %d", k, q.slot);
+    const long per = (long)q.C * q.I * q.S;
+    FOCAL_CHECK_ARG(per < (1L << 30), "mixup_multi: problem %d has %ld values per sample (less than 2^30)", k, per);
+    tab.p[k] = q;
+    tab.vec[k] = (per % 4 == 0 && ((uintptr_t)q.x % 16) == 0 && ((uintptr_t)q.y % 16) == 0) ? 1 : 0;
+    const long items = tab.vec[k] ? per / 4 : per;
+    max_items = items > max_items ? items : max_items;
+  }
+  long gx = (max_items + 255) / 256;
+  if (gx > 64) gx = 64;
+  FOCAL_LAUNCH(mixup_multi_kernel, dim3((int)gx, problems[0].B, n), dim3(256), 0, (hipStream_t)stream, tab, rec, perm);
+  FOCAL_LAUNCH_CHECK();
+  return FOCAL_OK;
+}

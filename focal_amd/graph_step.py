@@ -19,7 +19,11 @@ AdamW step counter advance on the device, the learning rate is a device word: re
 `CapturedTrainStep` is the training loop's wrapper: what stays eager per step is the part whose kernel sequence depends on host draws
 -- the two augmented views (Augmenter.forward("random"): one DFT launch per modality and view, plus a warp pass when drawn), written
 into address-stable two-view buffers (`Augmenter.static_views`) that the captured step reads.  A batch of another shape (the last
-batch of an epoch) runs eagerly."""
+batch of an epoch) runs eagerly.
+
+`CapturedClassifierStep` / `ClassifierSegments` are the same for the supervised and finetune stages (train_utils/supervised_train.py,
+finetune.py): [zero_grad -> fixed pipeline drawn on the device | plain transform -> classifier -> cross-entropy -> backward -> AdamW] as
+one hipGraph on one rank, batch and labels copied into static buffers in front of a replay."""
 import logging
 import os
 
@@ -341,7 +345,10 @@ def agree(ok, device):
     return bool(int(flag.item()))
 
 
-class CapturedTrainStep:
+class _CapturedStep:
+    """What the captured steps share: warm up eagerly, capture once the same key has come round `warm_steps` times, replay while the key
+    holds, run a step of another key eagerly, and fall back to eager (saying so once) when the capture fails."""
+
     def __init__(self, model, loss_func, optimizer, warm_steps=2, enabled=True):
         self.model, self.loss_func, self.opt = model, loss_func, optimizer
         # cross-rank BatchNorm statistics (DeepSense, -sync_bn) put collectives INSIDE the backbone passes: nothing there to cut a
@@ -352,37 +359,6 @@ class CapturedTrainStep:
         self.segments = None
         self.loss = None
         self.replays = self.eager_steps = 0
-
-    @staticmethod
-    def _key(v1, v2):
-        return tuple((t.data_ptr(), tuple(t.shape)) for v in (v1, v2) for mods in v.values() for t in mods.values())
-
-    def _segments(self, v1, v2):
-        dev = next(iter(next(iter(v1.values())).values())).device
-        return StepSegments(self.model, self.loss_func, self.opt, lambda: (v1, v2), dev)
-
-    def __call__(self, v1, v2):
-        """One optimiser step on the two views; returns the (device) loss of the step."""
-        return self._step(self._key(v1, v2), lambda: self._segments(v1, v2), lambda: None)
-
-    def step_from_inputs(self, augmenter, time_loc_inputs):
-        """One optimiser step on a batch of TIME-domain windows (device tensors): the two random views are drawn on the device inside
-        the step (Augmenter.forward_random_pair), so the replayed graph holds the whole reference loop body -- augmenter x 2, backbone,
-        loss, backward, optimizer.  The batch is copied into address-stable input buffers in front of the replay (one device-to-device
-        copy per modality; a loader that already fills fixed device buffers could hand those over instead)."""
-        flat = [(loc, mod) for loc in time_loc_inputs for mod in time_loc_inputs[loc]]
-        key = ("time",) + tuple((loc, mod, tuple(time_loc_inputs[loc][mod].shape)) for loc, mod in flat)
-        st = self.__dict__.setdefault("_static_inputs", {})
-        if key not in st:
-            st[key] = {loc: {mod: torch.empty_like(t, dtype=torch.float32).contiguous() for mod, t in mods.items()}
-                       for loc, mods in time_loc_inputs.items()}
-        static = st[key]
-
-        def load():
-            for loc, mod in flat:
-                static[loc][mod].copy_(time_loc_inputs[loc][mod], non_blocking=True)
-        dev = static[flat[0][0]][flat[0][1]].device
-        return self._step(key, lambda: StepSegments(self.model, self.loss_func, self.opt, lambda: augmenter.forward_random_pair(static), dev), load)
 
     def _step(self, key, make_segments, load_inputs):
         load_inputs()
@@ -425,3 +401,104 @@ class CapturedTrainStep:
             replay = seg.capture(side)
         torch.cuda.synchronize()
         self.segments, self.loss, self.replay = seg, seg.loss, replay
+
+
+class CapturedTrainStep(_CapturedStep):
+    @staticmethod
+    def _key(v1, v2):
+        return tuple((t.data_ptr(), tuple(t.shape)) for v in (v1, v2) for mods in v.values() for t in mods.values())
+
+    def _segments(self, v1, v2):
+        dev = next(iter(next(iter(v1.values())).values())).device
+        return StepSegments(self.model, self.loss_func, self.opt, lambda: (v1, v2), dev)
+
+    def __call__(self, v1, v2):
+        """One optimiser step on the two views; returns the (device) loss of the step."""
+        return self._step(self._key(v1, v2), lambda: self._segments(v1, v2), lambda: None)
+
+    def step_from_inputs(self, augmenter, time_loc_inputs):
+        """One optimiser step on a batch of TIME-domain windows (device tensors): the two random views are drawn on the device inside
+        the step (Augmenter.forward_random_pair), so the replayed graph holds the whole reference loop body -- augmenter x 2, backbone,
+        loss, backward, optimizer.  The batch is copied into address-stable input buffers in front of the replay (one device-to-device
+        copy per modality; a loader that already fills fixed device buffers could hand those over instead)."""
+        flat = [(loc, mod) for loc in time_loc_inputs for mod in time_loc_inputs[loc]]
+        key = ("time",) + tuple((loc, mod, tuple(time_loc_inputs[loc][mod].shape)) for loc, mod in flat)
+        st = self.__dict__.setdefault("_static_inputs", {})
+        if key not in st:
+            st[key] = {loc: {mod: torch.empty_like(t, dtype=torch.float32).contiguous() for mod, t in mods.items()}
+                       for loc, mods in time_loc_inputs.items()}
+        static = st[key]
+
+        def load():
+            for loc, mod in flat:
+                static[loc][mod].copy_(time_loc_inputs[loc][mod], non_blocking=True)
+        dev = static[flat[0][0]][flat[0][1]].device
+        return self._step(key, lambda: StepSegments(self.model, self.loss_func, self.opt, lambda: augmenter.forward_random_pair(static), dev), load)
+
+
+class ClassifierSegments(StepSegments):
+    """The classifier step of the supervised and finetune stages [zero_grad -> inputs() -> model(freq_x) -> cross-entropy(logits, labels)
+    -> backward -> optimizer.step] -- one rank (train.py refuses these stages data-parallel), so ONE hipGraph, captured twice into one
+    pool as the pretraining step is.  inputs(): -> (freq_x, labels), called inside the step: the `fixed` pipeline drawn on the device
+    (Augmenter.forward_fixed_device), the plain transform (finetune), or spectra somebody wrote eagerly in front of the step.
+    Finetune: the model runs its frozen encoders under no_grad itself, so only the head's node and the Adam step record work."""
+
+    def run(self):
+        self.opt.zero_grad()
+        freq_x, labels = self.views()
+        logits = self.model(freq_x)
+        self.logits = logits.detach()  # (kept as the loss is: a replay writes the same pool address)
+        loss = self.loss_fn(logits, labels)
+        self._backward(loss)
+        self._keep_loss(loss)
+        self.opt.step(reduce=False)
+
+    def capture(self, stream):
+        self.opt.sync_lr()
+        return self._capture_all(stream, False)
+
+
+class CapturedClassifierStep(_CapturedStep):
+    """CapturedTrainStep's counterpart for `train.py -learn_framework=no` and `-stage=finetune`: same warm-up, key, fallback and
+    counters.  The labels of a step are copied into a static buffer in front of it (a replay reads them there)."""
+
+    def _static(self, key, make):
+        st = self.__dict__.setdefault("_static_buffers", {})
+        if key not in st:
+            st[key] = make()
+        return st[key]
+
+    def _labels(self, labels, device):
+        """(key part, static buffer, the copy into it) of a step's labels: class indices [B] or one-hot / soft rows [B, n]."""
+        key = (tuple(labels.shape), labels.dtype)
+        buf = self._static(("labels",) + key, lambda: torch.empty(labels.shape, dtype=labels.dtype, device=device))
+        return key, buf, lambda: buf.copy_(labels, non_blocking=True)
+
+    def __call__(self, freq_x, labels):
+        """One optimiser step on spectra produced eagerly in front of it (host-drawn `fixed` pipeline); captured once the same
+        addresses have come round, as CapturedTrainStep.__call__ is -- the producer must write address-stable outputs
+        (Augmenter.static_fixed).  Returns the (device) loss of the step."""
+        dev = next(iter(next(iter(freq_x.values())).values())).device
+        lkey, lbuf, load = self._labels(labels, dev)
+        key = ("freq", lkey) + tuple((t.data_ptr(), tuple(t.shape)) for mods in freq_x.values() for t in mods.values())
+        return self._step(key, lambda: ClassifierSegments(self.model, self.loss_func, self.opt, lambda: (freq_x, lbuf), dev), load)
+
+    def step_from_inputs(self, augmenter, time_loc_inputs, labels, option="fixed"):
+        """One optimiser step on a batch of TIME-domain windows (device tensors) and its labels, both copied into static buffers; the
+        step holds the augmenter: option "fixed" = the supervised pipeline with every draw on the device (forward_fixed_device),
+        "no" = the plain transform (finetune)."""
+        if option not in ("fixed", "no"):
+            raise ValueError(f"step_from_inputs: option {option!r} (fixed or no)")
+        flat = [(loc, mod) for loc in time_loc_inputs for mod in time_loc_inputs[loc]]
+        dev = time_loc_inputs[flat[0][0]][flat[0][1]].device
+        lkey, lbuf, load_labels = self._labels(labels, dev)
+        key = ("time", option, lkey) + tuple((loc, mod, tuple(time_loc_inputs[loc][mod].shape)) for loc, mod in flat)
+        static = self._static(key, lambda: {loc: {mod: torch.empty_like(t, dtype=torch.float32).contiguous() for mod, t in mods.items()}
+                                            for loc, mods in time_loc_inputs.items()})
+
+        def load():
+            for loc, mod in flat:
+                static[loc][mod].copy_(time_loc_inputs[loc][mod], non_blocking=True)
+            load_labels()
+        transform = augmenter.forward_fixed_device if option == "fixed" else augmenter.fft_preprocess
+        return self._step(key, lambda: ClassifierSegments(self.model, self.loss_func, self.opt, lambda: (transform(static), lbuf), dev), load)

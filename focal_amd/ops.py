@@ -443,6 +443,65 @@ def mixup(x, perm, lam=1.0, box=None):
     return y
 
 
+# ---- Mixup drawn on the device (focal_mixup_draw / focal_mixup_multi: include/focal_hip.h)
+MIX_RECORD_BYTES = C.sizeof(_lib.MixRecord)
+
+
+def new_mix_record(device):
+    """uint8 [sizeof(focal_mix_record)]; zero = apply 0, which focal_mixup_multi copies through."""
+    return torch.zeros(MIX_RECORD_BYTES, dtype=torch.uint8, device=device)
+
+
+def read_mix_record(rec):
+    """Host copy of the record (tests, diagnostics): a _lib.MixRecord."""
+    return _lib.MixRecord.from_buffer_copy(rec.cpu().numpy().tobytes())
+
+
+def write_mix_record(rec, apply=1, cut=0, lam=1.0, boxes=()):
+    """Force a record (tests); boxes = [(yl, yh, xl, xh)] per slot."""
+    r = _lib.MixRecord()
+    r.apply, r.cut, r.lam = int(apply), int(cut), float(lam)
+    for q, box in enumerate(boxes):
+        for k in range(4):
+            r.box[q][k] = int(box[k])
+    rec.copy_(torch.frombuffer(bytearray(bytes(r)), dtype=torch.uint8))
+
+
+def mixup_draw(cfg, B, slots, state, stream_id, rec, perm, advance=True):
+    """The draws of one Mixup call in mode "random_batch" on the device: cfg = the dataset config's `mixup` section (prob, switch_prob,
+    mixup_alpha, cutmix_alpha), slots = [(I, S)] of the (location, modality) tensors, state = 4 int32 device words {seed, draw count, 0, 0}
+    (advance: the kernel moves them on), rec = new_mix_record, perm = int32 [B] device."""
+    _need_cuda(rec, perm, state)
+    assert rec.dtype == torch.uint8 and rec.numel() == MIX_RECORD_BYTES and perm.dtype == torch.int32 and perm.numel() >= B
+    assert state is None or (state.dtype == torch.int32 and state.numel() >= 4)
+    n = len(slots)
+    Is, Ss = (C.c_int * max(n, 1))(*[int(s[0]) for s in slots]), (C.c_int * max(n, 1))(*[int(s[1]) for s in slots])
+    check(_lib.load().focal_mixup_draw(float(cfg["prob"]), float(cfg["switch_prob"]), float(cfg["mixup_alpha"]), float(cfg["cutmix_alpha"]),
+                                       int(B), n, Is, Ss, _p(state), int(bool(advance)), int(stream_id) & 0xFFFFFFFF, _p(rec), _p(perm),
+                                       _stream()))
+
+
+def mixup_multi(items, rec, perm):
+    """items: [dict(x=fp32 [B, C, I, S], y=like x | None, slot=)] -- every (location, modality) tensor of a step mixed in ONE launch as the
+    device record and permutation say when the kernel runs (focal_mixup_multi) -> the list of outputs."""
+    _need_cuda(rec, perm)
+    assert rec.dtype == torch.uint8 and rec.numel() == MIX_RECORD_BYTES and perm.dtype == torch.int32
+    arr = (_lib.MixProblem * max(len(items), 1))()
+    outs = []
+    for q, it in zip(arr, items):
+        x = it["x"]
+        y = it.get("y")
+        if y is None:
+            y = torch.empty_like(x)
+        _need_cuda(x, y)
+        assert x.dtype == torch.float32 and y.dtype == torch.float32 and y.shape == x.shape and x.dim() == 4 and perm.numel() >= x.shape[0]
+        q.B, q.C, q.I, q.S = x.shape
+        q.x, q.y, q.slot = _p(x), _p(y), int(it.get("slot", 0))
+        outs.append(y)
+    check(_lib.load().focal_mixup_multi(len(items), arr, _p(rec), _p(perm), _stream()))
+    return outs
+
+
 # ------------------------------------------------------------------------------------------------ row 8
 def pad_patch_embed_ln(x, w, b, gamma, beta, Hp, Wp, pw, eps=1e-5, next_ln=None):
     """next_ln = (gamma2, beta2, out_dtype): also return (LayerNorm(tokens), stats) of the LayerNorm that follows (C0 == 64)."""

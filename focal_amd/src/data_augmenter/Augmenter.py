@@ -9,6 +9,9 @@ host, unseeded as in the reference.
 DEVICE (`focal_view_draw`: the augmenter of each view, the per-(location, modality) coins, scale factors, interval orders, phase
 angles, warp knots), the warp tables built on the device (`focal_warp_plan_multi`) and the transforms reading their augmentation
 from the drawn records -- launches of fixed shape, so the views are part of the captured step and a replay draws fresh ones.
+`forward_fixed_device(time_loc_inputs)` is the same for the supervised `fixed` pipeline: Mixup's draws (`focal_mixup_draw`), the mix of
+all modalities (`focal_mixup_multi`), the phase-shift draw and one transform call, a fixed launch sequence inside the captured
+classifier step; `forward_fixed` keeps the host-drawn form.
 `time_warp` / `mag_warp` wrap tsai's random-spline transforms, whose source is not available in this build environment: they
 are restated from tsai's published algorithm in focal_amd/warp.py (the curve, drawn on the host like every other augmenter's
 randomness) and run as one device pass in front of the transform (focal_warp_fwd); see that module for the one documented
@@ -261,7 +264,8 @@ class Augmenter:
             for loc in d:
                 for mod in d[loc]:
                     kw[loc][mod].update(d[loc][mod])
-        return _transform_all({loc: {mod: dict(x=t.contiguous(), **kw[loc][mod]) for mod, t in mods.items()} for loc, mods in x.items()})
+        return _transform_all({loc: {mod: dict(x=t.contiguous(), out=self._static_out(loc, mod, t), **kw[loc][mod]) for mod, t in mods.items()}
+                               for loc, mods in x.items()})
 
     def forward_random(self, time_loc_inputs):
         """ONE augmenter from the (time + freq) pool per call (reference :76-113); its arithmetic runs inside the DFT kernel."""
@@ -358,6 +362,80 @@ class Augmenter:
                 views[v][l][m] = outs[v * n + i]
         return views
 
+    # ------------------------------------------------------------------------------------------ the fixed pipeline, drawn on the device
+    FIXED_MIX_STREAM, FIXED_VIEW_STREAM = 0x4D495846, 0x46495856   # ("MIXF", "FIXV": apart from the random views' 0x56494557)
+
+    def fixed_device_draws_supported(self):
+        """The `fixed` pipeline is made of what focal_mixup_draw / focal_view_draw know (every shipped `fixed_augmenters` is):
+        mixup / no in the time domain, phase_shift / no after the transform, Mixup in mode "random_batch" without cutmix_minmax."""
+        cfg = self.args.dataset_config
+        if not (set(self.time_aug_names) <= {"no", "mixup"} and set(self.freq_aug_names) <= {"no", "phase_shift"}):
+            return False
+        if "mixup" in self.time_aug_names:
+            mc = cfg.get("mixup", {})
+            if mc.get("mode", "batch") != "random_batch" or mc.get("cutmix_minmax") is not None:
+                return False
+        return len(cfg["location_names"]) * len(cfg["modality_names"]) <= ops._lib.VIEW_MAX_SLOTS
+
+    def _fixed_state(self, inputs):
+        """What forward_fixed_device writes, ONE state per batch shape and never dropped, for the reason _device_state gives: a captured
+        step holds the addresses of the record, the permutation, the plans, the mixed windows and the spectra."""
+        flat = [(loc, mod) for loc in inputs for mod in inputs[loc]]
+        key = tuple((loc, mod, tuple(inputs[loc][mod].shape), inputs[loc][mod].device) for loc, mod in flat)
+        states = self.__dict__.setdefault("_fixed_states", {})
+        st = states.get(key)
+        if st is not None:
+            return st
+        from focal_amd import runtime
+        cfg = self.args.dataset_config
+        dev = inputs[flat[0][0]][flat[0][1]].device
+        shape = lambda k: tuple(inputs[k[0]][k[1]].shape)
+        phase = "phase_shift" in self.freq_aug_names
+        st = {"key": key, "flat": flat, "mix": "mixup" in self.time_aug_names, "B": shape(flat[0])[0],
+              "rec": ops.new_mix_record(dev), "perm": torch.zeros(shape(flat[0])[0], dtype=torch.int32, device=dev),
+              "mixed": {k: torch.empty(shape(k), dtype=torch.float32, device=dev) for k in flat},
+              # a one-entry pool: the view draw's per-slot coin is the augmenter's own (PhaseShiftAugmenter.py: random() < prob)
+              "pool": ops.view_pool([("phase_shift", cfg["phase_shift"]["prob"])] if phase else [("no", 0.0)], [shape(k)[2] for k in flat]),
+              "plans": ops.new_view_plans(1, len(flat), dev),
+              "out": {k: torch.empty((shape(k)[0], 2 * shape(k)[1]) + shape(k)[2:], dtype=torch.float32, device=dev) for k in flat},
+              "draw_state": runtime.view_state(dev)}
+        states[key] = st
+        return st
+
+    def forward_fixed_device(self, time_loc_inputs):
+        """forward_fixed with every draw made on the DEVICE, as one fixed sequence of launches (so the pipeline sits inside a captured
+        step and a replay draws anew): the mix draw (focal_mixup_draw), the mix pass of all slots (focal_mixup_multi; when `mixup` is
+        configured), the phase draw (focal_view_draw over a one-entry pool, one view), ONE transform call over all slots that reads the
+        drawn plans.  Inputs: fp32 [B, C, I, S] device tensors; returns address-stable spectra.  Labels are not touched: the reference
+        resets them before the frequency stage (see forward_fixed)."""
+        x = {loc: {mod: t.contiguous() for mod, t in mods.items()} for loc, mods in time_loc_inputs.items()}
+        st = self._fixed_state(x)
+        flat, n = st["flat"], len(st["flat"])
+        src = {k: x[k[0]][k[1]] for k in flat}
+        if st["mix"]:
+            ops.mixup_draw(self.args.dataset_config["mixup"], st["B"], [src[k].shape[2:] for k in flat], st["draw_state"],
+                           self.FIXED_MIX_STREAM, st["rec"], st["perm"])
+            ops.mixup_multi([dict(x=src[k], y=st["mixed"][k], slot=i) for i, k in enumerate(flat)], st["rec"], st["perm"])
+            src = st["mixed"]
+        ops.view_draw_shared(st["pool"], 1, n, st["draw_state"], self.FIXED_VIEW_STREAM, st["plans"])
+        outs = ops.fft_realpack_multi([dict(x=src[k], plan=st["plans"][i], x_warped=src[k], out=st["out"][k]) for i, k in enumerate(flat)])
+        res = {loc: {} for loc in x}
+        for (loc, mod), o in zip(flat, outs):
+            res[loc][mod] = o
+        return res
+
+    def _static_out(self, loc, mod, x):
+        """`static_fixed` (set by a loop that replays the classifier step behind host-drawn spectra): the spectrum of a (location,
+        modality) keeps its address per batch shape, so the captured step can read it.  Off (the default): a fresh tensor per call."""
+        if not getattr(self, "static_fixed", False):
+            return None
+        pool = self.__dict__.setdefault("_static_fixed_out", {})
+        shape = (x.shape[0], 2 * x.shape[1], x.shape[2], x.shape[3])
+        key = (loc, mod, shape, x.device)
+        if key not in pool:
+            pool[key] = torch.empty(shape, dtype=torch.float32, device=x.device)
+        return pool[key]
+
     def begin_step(self):
         """Called by the training loop before the first of a step's two draws (static_views): the next draw of every tensor gets the FIRST
         half again.  Without it an odd number of draws on a training-shaped batch -- an exception between the two draws, a caller that
@@ -401,4 +479,5 @@ class Augmenter:
 
     def fft_preprocess(self, time_loc_inputs):
         """[b, c, i, s] real -> [b, 2c, i, s] packed spectrum (reference :141-158), on the HIP DFT kernel."""
-        return _transform_all({loc: {mod: dict(x=x.contiguous()) for mod, x in mods.items()} for loc, mods in time_loc_inputs.items()})
+        return _transform_all({loc: {mod: dict(x=x.contiguous(), out=self._static_out(loc, mod, x)) for mod, x in mods.items()}
+                               for loc, mods in time_loc_inputs.items()})

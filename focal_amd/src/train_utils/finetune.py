@@ -11,6 +11,7 @@ from general_utils.weight_utils import load_model_weight, set_learnable_params_f
 from train_utils.eval_functions import val_and_logging
 from train_utils.lr_scheduler import define_lr_scheduler
 from train_utils.optimizer import define_optimizer
+from train_utils.supervised_train import CapturedClassifierStep, classifier_step_form, run_classifier_epoch
 
 
 def finetune(args, classifier, augmenter, train_dataloader, val_dataloader, test_dataloader, classifier_loss_func, num_batches):
@@ -27,17 +28,27 @@ def finetune(args, classifier, augmenter, train_dataloader, val_dataloader, test
     start = time_sync()
     best_val_acc, val_epochs = 0, 5
     epochs = getattr(args, "epochs", None) or args.dataset_config[args.learn_framework]["finetune_lr_scheduler"]["train_epochs"]
+    # the step [transform -> frozen encoders -> head -> cross-entropy -> backward -> Adam] is replayed from a hipGraph once its shapes
+    # have repeated (focal_amd/graph_step.py: CapturedClassifierStep); this stage has no draws, so -host_draws only keeps the transform
+    # eager in front of the captured body
+    graph, host_draws = classifier_step_form(args, augmenter, "no")
+    graphed = CapturedClassifierStep(classifier, classifier_loss_func, optimizer, enabled=graph)
+    logging.info(f"classifier step: {'replayed from a hipGraph' if graph else 'launched eagerly'}; transform "
+                 f"{'in front of the step' if host_draws else 'inside the step'}")
+
+    def parent_step(time_loc_inputs, labels):
+        aug_freq_loc_inputs, labels = augmenter.forward("no", time_loc_inputs, labels)
+        logits = classifier(aug_freq_loc_inputs)
+        loss = classifier_loss_func(logits, labels)
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        return loss.item()
+
     for epoch in range(epochs):
         classifier.train()
-        train_loss_list = []
-        for i, (time_loc_inputs, labels) in enumerate(train_dataloader):
-            aug_freq_loc_inputs, labels = augmenter.forward("no", time_loc_inputs, labels)
-            logits = classifier(aug_freq_loc_inputs)
-            loss = classifier_loss_func(logits, labels)
-            optimizer.zero_grad()
-            loss.backward()
-            optimizer.step()
-            train_loss_list.append(loss.item())
+        train_loss_list = run_classifier_epoch(graphed, augmenter, train_dataloader, "no", graph, host_draws, parent_step)
+        logging.info(f"epoch {epoch}: {graphed.replays} graph replays, {graphed.eager_steps} eager steps so far")
         if epoch % val_epochs == 0:
             val_metric, val_loss = val_and_logging(args, epoch, classifier, augmenter, val_dataloader, test_dataloader,
                                                   classifier_loss_func, float(np.mean(train_loss_list)))

@@ -228,6 +228,52 @@ int focal_warp_fwd(int rows, int L, const float* x, const float* mult, const int
 int focal_mixup_fwd(int B, int C, int I, int S, const float* x, const int* perm, float lam, int cut, int yl, int yh, int xl, int xh,
                     float* y, void* stream);
 
+/* Mixup's draws on the device (the host draws of Mixup._params_per_batch + _mix_batch_random + rand_bbox, input_utils/mixup_utils.py:154-176,
+ * :252-281, :32-54, mode "random_batch"), so that the `fixed` pipeline sits inside a captured step: ONE launch of ONE workgroup writes a
+ * focal_mix_record and the batch permutation, both in device memory, which focal_mixup_multi reads when it runs.
+ * state: 4 device words {seed, draw count, 0, 0} as for focal_view_draw; advance = 1: the kernel moves them on after everybody has read them
+ * (seed <- mix32(seed + 0x9E3779B9), count += 1), so every replay of a captured step draws a new mix.  advance = 0: read only; NULL = seed 0.
+ * With mix32 as stated beside the jitter noise, uint32 arithmetic throughout, s = state[0]:
+ *   km   = mix32(s * 0x9E3779B9 + stream_id * 0x85EBCA6B + 0x4D495855)                      the key of this draw
+ *   r(i) = mix32(km + i * 0x85EBCA6B),  u(i) = (r(i) >> 8) / 2^24 in [0, 1)                  draw i (vd_uniform of the view draws)
+ *   n(i) = sqrt(-2 ln(1 - u(2i))) cos(2 pi u(2i + 1))                                        (vd_normal: Box-Muller on draws 2i, 2i + 1)
+ *   apply = u(0) < prob
+ *   cut   = u(1) < switch_prob when mixup_alpha > 0 and cutmix_alpha > 0, else cutmix_alpha > 0
+ *   lam ~ Beta(a, a), a = cut ? cutmix_alpha : mixup_alpha:
+ *     a == 1: lam = u(2), exactly one uniform draw.
+ *     else  : lam = G0 / (G0 + G1), two Gamma(a) draws by Marsaglia-Tsang, Gg (g = 0, 1): a' = a < 1 ? a + 1 : a, d = a' - 1/3,
+ *             c = 1 / sqrt(9 d); try t = 0 .. FOCAL_MIX_GAMMA_TRIES - 1: x = n(32 + 16 g + t), v = (1 + c x)^3, w = 1 - u(128 + 16 g + t);
+ *             accepted when v > 0 and ln w < x^2 / 2 + d - d v + d ln v, then Gg = d v, times (1 - u(4 + g))^(1 / a) when a < 1 (the boost).
+ *             If either draw runs out of tries (probability < 0.05^16 each) lam = 0.5, the distribution's mean.  A NaN or 0 / 0 gives 0.5 too.
+ *   perm: key kp = mix32(km ^ 0x5045524D), h(b) = mix32(kp + b * 0x85EBCA6B) for b in [0, B);
+ *         perm[b] = #{ j : h(j) < h(b), or h(j) == h(b) and j < b } -- the rank of sample b's hash, ties broken by index: a uniformly random
+ *         permutation (up to hash ties, 2^-32 a pair), computed by all threads at once; ONE permutation for all slots, as the reference's.
+ *   box of slot q (its tensor is [B, C, I, S]; written when cut, all in fp32 as rand_bbox's numpy arithmetic rounds):
+ *         ratio = sqrtf(1 - lam), cut_h = (int)((float)I * ratio), cut_w = (int)((float)S * ratio),
+ *         cy = min((int)(u(8 + 2 q) * (float)I), I - 1), cx = min((int)(u(9 + 2 q) * (float)S), S - 1),
+ *         yl = clip(cy - cut_h / 2, 0, I), yh = clip(cy + cut_h / 2, 0, I), xl = clip(cx - cut_w / 2, 0, S), xh = clip(cx + cut_w / 2, 0, S)
+ *   apply == 0: the record is the identity (apply = cut = 0, lam = 1, every box 0 0 0 0) and perm is still written.
+ *   apply == 1, cut == 0: the boxes are 0 0 0 0 (the reference draws none).  Slots >= n_slots: 0 0 0 0.
+ * Checked on the host: prob, switch_prob in [0, 1]; an alpha > 0 (neither negative); 1 <= B <= FOCAL_MIX_MAX_BATCH; 1 <= n_slots <=
+ * FOCAL_VIEW_MAX_SLOTS; every I, S >= 1. */
+#define FOCAL_MIX_MAX_BATCH 4096
+#define FOCAL_MIX_GAMMA_TRIES 16
+typedef struct { int apply; int cut; float lam; int box[FOCAL_VIEW_MAX_SLOTS][4]; /* yl, yh, xl, xh */ } focal_mix_record;
+int focal_mixup_draw(float prob, float switch_prob, float mixup_alpha, float cutmix_alpha, int B, int n_slots, const int* I, const int* S,
+                     uint32_t* state, int advance, uint32_t stream_id, focal_mix_record* rec, int* perm, void* stream);
+/* The mix pass of all slots of a step in ONE launch, reading the DEVICE record and permutation when the kernel runs.  Per problem
+ * x, y fp32 [B, C, I, S] (y != x; every problem has the batch's B), slot = which box of the record is this tensor's.  focal_mixup_fwd's
+ * arithmetic, the same expressions: cut = 0: y[b] = lam * x[b] + (1 - lam) * x[perm[b]]; cut = 1: the box of x[perm[b]] pasted into x[b];
+ * apply = 0: y = x, copied through (the launch sequence of a step never depends on the draw).  The sample index comes from the grid; 16-byte
+ * loads and stores where C*I*S % 4 == 0 and x, y are 16-byte aligned, scalar otherwise.  A device record cannot be checked by the host,
+ * so the kernel clamps what it says before it moves a read: perm entries to [0, B), box bounds to [0, I] / [0, S]. */
+typedef struct { int B, C, I, S; const float* x; float* y; int slot; } focal_mix_problem;
+int focal_mixup_multi(int n, const focal_mix_problem* problems, const focal_mix_record* rec, const int* perm, void* stream);
+#ifdef __cplusplus
+static_assert(sizeof(focal_mix_record) == 140, "focal_mix_record");
+static_assert(sizeof(focal_mix_problem) == 40, "focal_mix_problem");
+#endif
+
 /* ------------------------------------------------------------------------------------------------ row 8: embed
  * SW_Transformer.pad_input + PatchEmbed (models/SW_Transformer.py:184-208, models/SwinModules.py:547-558):
  * zero-pad [B, cin, I, S] to (Hp*1, Wp*pw), Conv2d(cin -> C0, kernel = stride = [1, pw]), flatten, LayerNorm.
