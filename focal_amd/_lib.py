@@ -150,6 +150,11 @@ class AdamWDesc(C.Structure):
     _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("l2_decay", C.c_int)]
 
 
+# gradient clipping (include/focal_hip.h: focal_grad_norm_multi): segments and workgroups of one norm launch, words of the partial row,
+# words of the record {steps, clipped, skipped, sum of norms, max norm, last norm, last sum of squares, last coef}
+CLIP_MAX_SEGMENTS, MAX_BLOCKS, CLIP_SCRATCH_WORDS, CLIP_RECORD_WORDS = 8, 1024, 1024, 8
+
+
 class TraceRecord(C.Structure):
     _fields_ = [("kernel", C.c_char * 384), ("grid", C.c_uint * 3), ("block", C.c_uint * 3), ("stream", C.c_void_p), ("us", C.c_float)]
 
@@ -238,6 +243,12 @@ PROTOTYPES = {
                                     C.POINTER(P), C.POINTER(P), C.POINTER(C.c_long), P, P, P]),
     "focal_adamw_multi_advance": (C.c_int, [C.POINTER(AdamWDesc), C.c_int, C.POINTER(P), C.POINTER(P), C.POINTER(P),
                                             C.POINTER(P), C.POINTER(P), C.POINTER(C.c_long), P, P, C.c_int, P, P]),
+    "focal_grad_norm_multi": (C.c_int, [C.c_int, C.POINTER(P), C.POINTER(C.c_long), P, C.c_int, P]),
+    "focal_adamw_clip_multi": (C.c_int, [C.POINTER(AdamWDesc), C.c_int, C.POINTER(P), C.POINTER(P), C.POINTER(P),
+                                         C.POINTER(P), C.POINTER(P), C.POINTER(C.c_long), P, P, P, C.c_int, P, C.c_int, C.c_float, P]),
+    "focal_adamw_clip_multi_advance": (C.c_int, [C.POINTER(AdamWDesc), C.c_int, C.POINTER(P), C.POINTER(P), C.POINTER(P),
+                                                 C.POINTER(P), C.POINTER(P), C.POINTER(C.c_long), P, P, C.c_int, P, P, C.c_int, P, C.c_int,
+                                                 C.c_float, P]),
     "focal_cast_bf16": (C.c_int, [P, P, C.c_long, P]),
     "focal_conv_in_fwd": (C.c_int, [C.POINTER(ConvInDesc), P, P, P, P, P]),
     "focal_conv_in_bwd_weight": (C.c_int, [C.POINTER(ConvInDesc), P, P, C.c_int, P, P, P]),

@@ -126,15 +126,58 @@ def cast_bf16(src, dst):
     check(_lib.load().focal_cast_bf16(_p(src), _p(dst), src.numel(), _stream()))
 
 
-def adamw_multi(segments, lr_dev, rng_state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.05, l2_decay=False, advance=False, seed_state=None):
+def new_clip_state(device):
+    """Device state of gradient clipping: (partial row of CLIP_SCRATCH_WORDS fp32 sums of squares, record of CLIP_RECORD_WORDS words)."""
+    return (torch.zeros(_lib.CLIP_SCRATCH_WORDS, dtype=torch.float32, device=device),
+            torch.zeros(_lib.CLIP_RECORD_WORDS, dtype=torch.int32, device=device))
+
+
+def grad_norm(segs, clip_state):
+    """The norm pass: per-workgroup sums of squares of the flat fp32 gradient tensors `segs` (lengths multiples of 4) into clip_state's
+    partial row, one launch; adamw_multi(..., clip=(clip_state, max_norm)) behind it turns the row into the norm and the coefficient."""
+    _need_cuda(*segs)
+    n = len(segs)
+    if any(g.dtype != torch.float32 for g in segs):
+        raise _lib.FocalHipError("grad_norm: gradients are fp32")
+    check(_lib.load().focal_grad_norm_multi(n, (C.c_void_p * max(n, 1))(*[_p(g) for g in segs]), (C.c_long * max(n, 1))(*[g.numel() for g in segs]),
+                                            _p(clip_state[0]), clip_state[0].numel(), _stream()))
+
+
+def read_clip_stats(clip_state):
+    """One device-to-host copy of the record, as a dict; the record is reset (call outside graph capture, e.g. once per epoch)."""
+    rec = clip_state[1].cpu()
+    clip_state[1].zero_()
+    f = rec.view(torch.float32)
+    steps, clipped, skipped = (int(v) for v in rec[:3])
+    return {"steps": steps, "clipped": clipped, "skipped": skipped, "norm_sum": float(f[3]), "norm_max": float(f[4]),
+            "norm_mean": float(f[3]) / max(steps - skipped, 1), "last_norm": float(f[5]), "last_sq": float(f[6]), "last_coef": float(f[7])}
+
+
+def adamw_multi(segments, lr_dev, rng_state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.05, l2_decay=False, advance=False, seed_state=None,
+                clip=None):
     """segments: list of (p, g, m, v, shadow_or_None) flat tensors (lengths multiples of 4).  rng_state[1] is the step count the update
     uses; advance=True: the count used is rng_state[1] + 1 and the kernel itself then advances rng_state and (if given) seed_state
-    (focal_adamw_multi_advance: what two focal_rng_advance launches in front of the call would have done)."""
+    (focal_adamw_multi_advance: what two focal_rng_advance launches in front of the call would have done).
+    clip=(clip_state, max_norm): the update on g * min(1, max_norm / (norm + 1e-6)), the norm from the partial row grad_norm() left in
+    clip_state; a non-finite norm skips the step (focal_adamw_clip_multi / _advance)."""
     n = len(segments)
     arr = lambda i: (C.c_void_p * n)(*[_p(s[i]) for s in segments])
     has_shadow = any(s[4] is not None for s in segments)
     lens = (C.c_long * n)(*[s[0].numel() for s in segments])
     d = AdamWDesc(beta1, beta2, eps, weight_decay, int(l2_decay))
+    if clip is not None:
+        (row, rec), max_norm = clip
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:  # refused here as well: a NaN or non-positive bound never reaches a launch
+            raise ValueError(f"adamw_multi: max_norm = {max_norm} must be positive (inf: clip nothing, record the norms)")
+        tail = (_p(row), row.numel(), _p(rec), rec.numel(), max_norm, _stream())
+        if advance:
+            check(_lib.load().focal_adamw_clip_multi_advance(C.byref(d), n, arr(0), arr(1), arr(2), arr(3), arr(4) if has_shadow else None,
+                                                             lens, _p(lr_dev), _p(rng_state), rng_state.numel(), _p(seed_state), *tail))
+            return
+        check(_lib.load().focal_adamw_clip_multi(C.byref(d), n, arr(0), arr(1), arr(2), arr(3), arr(4) if has_shadow else None,
+                                                 lens, _p(lr_dev), _p(rng_state), *tail))
+        return
     if advance:
         check(_lib.load().focal_adamw_multi_advance(C.byref(d), n, arr(0), arr(1), arr(2), arr(3), arr(4) if has_shadow else None,
                                                     lens, _p(lr_dev), _p(rng_state), rng_state.numel(), _p(seed_state), _stream()))

@@ -10,10 +10,19 @@ from . import distributed, ops, runtime
 
 
 class FocalAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, l2_decay=False):
-        """l2_decay=True gives torch.optim.Adam semantics (g += wd * p): the reference's finetune optimizer."""
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, l2_decay=False, max_grad_norm=None):
+        """l2_decay=True gives torch.optim.Adam semantics (g += wd * p): the reference's finetune optimizer.
+        max_grad_norm (None: off): torch.nn.utils.clip_grad_norm_(params, max_grad_norm) between backward and the update, inside step() --
+        a norm pass over the gradient spans and the update on g * coef, no host read; inf clips nothing and still records the norms
+        (clip_stats()).  A step whose gradient norm is not finite is skipped (torch would write NaN into the weights)."""
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError(f"FocalAdamW: max_grad_norm = {max_grad_norm} must be positive (inf: record the norms, clip nothing)")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._l2 = bool(l2_decay)
+        self.max_grad_norm = max_grad_norm
+        self._clip_state = None  # device (partial sums of squares, record): ops.new_clip_state
         self._lr_dev = None
         self._lr_host = None
         self._step_state = None  # device {., step}: this optimizer's own step counter (AdamW bias correction)
@@ -124,10 +133,24 @@ class FocalAdamW(torch.optim.Optimizer):
             m, v = ar.moments()
             lo, hi = self._span(ar)
             segs.append((ar.flat[lo:hi], ar.grad[lo:hi], m[lo:hi], v[lo:hi], ar.shadow[lo:hi] if ar.shadow is not None else None))
+        clip = None
+        if self.max_grad_norm is not None:
+            # behind the gradient reduction: every rank takes the norm of the same reduced gradient (no collective of its own)
+            if self._clip_state is None:
+                self._clip_state = ops.new_clip_state(dev)
+            ops.grad_norm([s[1] for s in segs], self._clip_state)
+            clip = (self._clip_state, self.max_grad_norm)
         ops.adamw_multi(segs, self._lr_dev, self._step_state, g0["betas"][0], g0["betas"][1], g0["eps"],
-                        g0["weight_decay"], self._l2, advance=True, seed_state=runtime.rng_state(dev))
+                        g0["weight_decay"], self._l2, advance=True, seed_state=runtime.rng_state(dev), clip=clip)
         for ar in arenas:
             ar.mark_shadow_fresh()
+
+    def clip_stats(self):
+        """Gradient-norm statistics since the last call (one device-to-host copy; the record is reset), or None with clipping off or
+        before the first step: {steps, clipped, skipped, norm_mean, norm_max, last_norm, ...} (ops.read_clip_stats)."""
+        if self._clip_state is None:
+            return None
+        return ops.read_clip_stats(self._clip_state)
 
     # ---- resume support (the reference saves weights only; SURVEY 8f rank 3 asks for optimizer state as well)
     def train_state(self):

@@ -10,7 +10,7 @@ from general_utils.time_utils import time_sync
 from general_utils.weight_utils import load_model_weight, set_learnable_params_finetune
 from train_utils.eval_functions import val_and_logging
 from train_utils.lr_scheduler import define_lr_scheduler
-from train_utils.optimizer import define_optimizer
+from train_utils.optimizer import define_optimizer, log_clip_stats
 from train_utils.supervised_train import CapturedClassifierStep, classifier_step_form, run_classifier_epoch
 
 
@@ -49,6 +49,7 @@ def finetune(args, classifier, augmenter, train_dataloader, val_dataloader, test
         classifier.train()
         train_loss_list = run_classifier_epoch(graphed, augmenter, train_dataloader, "no", graph, host_draws, parent_step)
         logging.info(f"epoch {epoch}: {graphed.replays} graph replays, {graphed.eager_steps} eager steps so far")
+        log_clip_stats(optimizer, epoch)
         if epoch % val_epochs == 0:
             val_metric, val_loss = val_and_logging(args, epoch, classifier, augmenter, val_dataloader, test_dataloader,
                                                   classifier_loss_func, float(np.mean(train_loss_list)))

@@ -7,21 +7,50 @@ _ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..", ".."
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
+import logging  # noqa: E402
+import math  # noqa: E402
+
 from focal_amd.optim import FocalAdamW  # noqa: E402
+
+
+def _max_grad_norm(args, cfg, section):
+    """-clip_grad: the section's `clip_grad` becomes the bound of the global gradient norm.  Without the switch the key is not read (the
+    reference never reads it, and the pinned trajectories follow the reference)."""
+    if not getattr(args, "clip_grad", False):
+        return None
+    value = cfg.get("clip_grad")
+    ok = isinstance(value, (int, float)) and not isinstance(value, bool) and not math.isnan(value) and value > 0
+    if not ok:
+        raise ValueError(f"-clip_grad: `{section}: clip_grad` of the dataset YAML is {value!r}; it must be a positive number "
+                         "(.inf records the gradient norms and clips nothing)")
+    return float(value)
 
 
 def define_optimizer(args, parameters):
     if args.train_mode in {"supervised"}:
+        section = f"{args.model}: optimizer"
         cfg = args.dataset_config[args.model]["optimizer"]
     elif args.stage == "pretrain":
+        section = f"{args.learn_framework}: pretrain_optimizer"
         cfg = args.dataset_config[args.learn_framework]["pretrain_optimizer"]
     elif args.stage == "finetune":
+        section = f"{args.learn_framework}: finetune_optimizer"
         cfg = args.dataset_config[args.learn_framework]["finetune_optimizer"]
     else:
         raise Exception("Optimizer not defined.")
     wd = cfg["weight_decay"][args.model] if isinstance(cfg["weight_decay"], dict) else cfg["weight_decay"]
+    clip = _max_grad_norm(args, cfg, section)
     if cfg["name"] == "AdamW":
-        return FocalAdamW(parameters, lr=cfg["start_lr"], weight_decay=wd)
+        return FocalAdamW(parameters, lr=cfg["start_lr"], weight_decay=wd, max_grad_norm=clip)
     if cfg["name"] == "Adam":  # torch.optim.Adam: L2 weight decay folded into the gradient (the finetune optimizer)
-        return FocalAdamW(parameters, lr=cfg["start_lr"], weight_decay=wd, l2_decay=True)
+        return FocalAdamW(parameters, lr=cfg["start_lr"], weight_decay=wd, l2_decay=True, max_grad_norm=clip)
     raise NotImplementedError(f"Optimizer {cfg['name']} not implemented.")
+
+
+def log_clip_stats(optimizer, epoch):
+    """With clipping on: one line per epoch from the device-side record (one read, where the epoch's last loss has just been read)."""
+    stats = optimizer.clip_stats() if getattr(optimizer, "max_grad_norm", None) is not None else None
+    if not stats or stats["steps"] == 0:
+        return
+    logging.info(f"epoch {epoch}: gradient norm mean {stats['norm_mean']:.4g}, max {stats['norm_max']:.4g}; {stats['clipped']} of "
+                 f"{stats['steps']} steps clipped, {stats['skipped']} skipped (max_norm {optimizer.max_grad_norm:g})")

@@ -18,7 +18,7 @@ from train_utils.knn import compute_knn
 from train_utils.loss_calc_utils import calc_pretrain_loss
 from train_utils.lr_scheduler import define_lr_scheduler
 from train_utils.model_selection import init_pretrain_framework
-from train_utils.optimizer import define_optimizer
+from train_utils.optimizer import define_optimizer, log_clip_stats
 
 _ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..", ".."))
 if _ROOT not in sys.path:
@@ -100,6 +100,7 @@ def pretrain(args, backbone_model, augmenter, train_dataloader, val_dataloader, 
             epoch_windows += n
         if pending is not None:
             train_loss_list.append(pending.item())
+        log_clip_stats(optimizer, epoch)
         if epoch % 10 == 0 or epoch == epochs - 1:
             dt = max(time_sync() - epoch_t0, 1e-9)
             logging.info(f"epoch {epoch}: {epoch_windows / dt:.1f} windows/s ({epoch_windows} windows in {dt:.3f} s; "

@@ -13,7 +13,7 @@ import torch
 from general_utils.time_utils import time_sync
 from train_utils.eval_functions import val_and_logging
 from train_utils.lr_scheduler import define_lr_scheduler
-from train_utils.optimizer import define_optimizer
+from train_utils.optimizer import define_optimizer, log_clip_stats
 
 _ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..", ".."))
 if _ROOT not in sys.path:
@@ -94,6 +94,7 @@ def supervised_train(args, classifier, augmenter, train_dataloader, val_dataload
         args.epoch = epoch
         train_loss_list = run_classifier_epoch(graphed, augmenter, train_dataloader, "fixed", graph, host_draws, parent_step)
         logging.info(f"epoch {epoch}: {graphed.replays} graph replays, {graphed.eager_steps} eager steps so far")
+        log_clip_stats(optimizer, epoch)
         if epoch % val_epochs == 0:
             val_metric, val_loss = val_and_logging(args, epoch, classifier, augmenter, val_dataloader, test_dataloader, loss_func,
                                                   float(np.mean(train_loss_list)))

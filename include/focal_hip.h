@@ -750,6 +750,35 @@ int focal_adamw_multi(const focal_adamw_desc* d, int nseg, float* const* p, cons
 int focal_adamw_multi_advance(const focal_adamw_desc* d, int nseg, float* const* p, const float* const* g, float* const* m,
                               float* const* v, void* const* shadow_bf16, const long* n, const float* lr_dev,
                               uint32_t* step_state, int step_state_words, uint32_t* seed_state, void* stream);
+/* Gradient clipping by global L2 norm (torch.nn.utils.clip_grad_norm_(params, max_norm, 2.0) between backward and the update), in two
+ * launches and without a host read.
+ *   focal_grad_norm_multi: one pass over up to FOCAL_CLIP_MAX_SEGMENTS gradient segments (lengths multiples of 4, as above).  At most
+ *     FOCAL_CLIP_MAX_BLOCKS workgroups of 256 lanes, one float4 per lane and trip of the grid-stride loop; workgroup b stores its sum
+ *     of squares into partials[b], the slots behind the grid are stored as zero: all FOCAL_CLIP_SCRATCH_WORDS words are written by
+ *     every call, in a fixed summation order (no atomics: the row is bit-repeatable).
+ *   focal_adamw_clip_multi / _advance: focal_adamw_multi / _advance on g * coef, coef = min(1, max_norm / (total_norm + 1e-6)) in
+ *     fp32, total_norm = sqrt(sum of the partials) -- every workgroup re-sums the row in the same order.  g * coef is rounded once
+ *     before anything is added to it: the result is bit-identical to the plain update on pre-scaled gradients, and to the plain
+ *     update on g when total_norm + 1e-6 <= max_norm (coef is then exactly 1; torch's formula, which already scales by
+ *     max_norm / (max_norm + 1e-6) at total_norm == max_norm, is kept as it is).  max_norm = +inf clips nothing and still records.
+ *     A non-finite total_norm SKIPS the step (clip_grad_norm_ would write NaN into every weight): p, m, v, shadow and the step count
+ *     stay as they are; the _advance form still advances seed_state.
+ *   record: FOCAL_CLIP_RECORD_WORDS 32-bit words, updated once per call (by the launch of the last non-empty segment), zeroed by the
+ *     reader: {u32 steps, u32 clipped steps, u32 skipped steps, f32 sum of the finite norms, f32 largest finite norm, f32 last norm,
+ *     f32 last sum of squares, f32 last coef (0 on a skipped step)}. */
+#define FOCAL_CLIP_MAX_SEGMENTS 8
+#define FOCAL_CLIP_MAX_BLOCKS 1024
+#define FOCAL_CLIP_SCRATCH_WORDS 1024
+#define FOCAL_CLIP_RECORD_WORDS 8
+int focal_grad_norm_multi(int nseg, const float* const* g, const long* n, float* partials, int partial_words, void* stream);
+int focal_adamw_clip_multi(const focal_adamw_desc* d, int nseg, float* const* p, const float* const* g, float* const* m,
+                           float* const* v, void* const* shadow_bf16, const long* n, const float* lr_dev,
+                           const uint32_t* rng_state, const float* partials, int partial_words, uint32_t* record, int record_words,
+                           float max_norm, void* stream);
+int focal_adamw_clip_multi_advance(const focal_adamw_desc* d, int nseg, float* const* p, const float* const* g, float* const* m,
+                                   float* const* v, void* const* shadow_bf16, const long* n, const float* lr_dev,
+                                   uint32_t* step_state, int step_state_words, uint32_t* seed_state, const float* partials,
+                                   int partial_words, uint32_t* record, int record_words, float max_norm, void* stream);
 /* fp32 -> bf16 cast of a weight segment (refreshing the shadow after load_state_dict) */
 int focal_cast_bf16(const float* src, void* dst, long n, void* stream);
 
