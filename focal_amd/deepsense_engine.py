@@ -455,8 +455,8 @@ class DeepSenseModEncoder:
     def finish_views(self, device):
         self.stack.finish_views(device)
 
-    def forward(self, x_freq, view, training):
-        c_out, csv = self.stack.forward(x_freq, view, training, getattr(self, "pass_order", None), getattr(self, "views_in_batch", 1))
+    def forward(self, x_freq, view, training, pass_order=None, views_in_batch=1):
+        c_out, csv = self.stack.forward(x_freq, view, training, pass_order, views_in_batch)
         feat, gsv = self.gru.forward(c_out, csv["B"], csv["I"], view, training)
         return feat, dict(conv=csv, gru=gsv)
 
@@ -496,11 +496,10 @@ class DeepSenseMultiLocEncoder:
         for st in self.stacks:
             st.finish_views(device)
 
-    def forward(self, xs, view, training):
-        order, G = getattr(self, "pass_order", None), getattr(self, "views_in_batch", 1)
+    def forward(self, xs, view, training, pass_order=None, views_in_batch=1):
         outs, saved = [], []
         for st, x in zip(self.first, xs):
-            c, csv = st.forward(x, view, training, order, G)
+            c, csv = st.forward(x, view, training, pass_order, views_in_batch)
             outs.append(c)
             saved.append(csv)
         B, I = saved[0]["B"], saved[0]["I"]
@@ -508,7 +507,7 @@ class DeepSenseMultiLocEncoder:
             raise ops._lib.FocalHipError("DeepSense: the first-level outputs of a modality must agree in shape (loc_mod_out_channels)")
         xm = ops.rows_mean(outs)  # [B*I, C1] = the [B, 1, I, C1] spectrum of the second block
         del outs
-        c2, csv2 = self.second.forward(xm.view(B, 1, I, self.geo["S"]), view, training, order, G)
+        c2, csv2 = self.second.forward(xm.view(B, 1, I, self.geo["S"]), view, training, pass_order, views_in_batch)
         feat, gsv = self.gru.forward(c2, B, I, view, training)
         return feat, dict(first=saved, second=csv2, gru=gsv)
 

@@ -8,7 +8,26 @@ Everything here is fp32 (activations of a few hundred KB); the products run on t
 import torch
 
 from . import ops
-from ._lib import ACT_NONE, EPI_GELU
+from ._lib import ACT_NONE, EPI_GELU, EPI_NONE
+
+
+def lin(code, x, w, b, epilogue=EPI_NONE, resid=None, drop=None):
+    """y [rows, n_out] fp32 = epilogue(x w^T + b), fp32 activations, `code` operands -> (y, the product's descriptor)."""
+    f32 = ops.code(torch.float32)
+    d = ops.linear_desc(code, x.shape[0], w.shape[0], x.shape[1], f32, f32, ACT_NONE, epilogue, out_drop=drop)
+    y = torch.empty(x.shape[0], w.shape[0], dtype=torch.float32, device=x.device)
+    ops.linear_fwd(d, x, w, b, resid, y)
+    return y, d
+
+
+def lin_bwd(d, dy, x, w, gw, gb, need_dx=True):
+    """Weight and bias gradients of lin() into gw / gb (the arena); -> dx, or None where nothing flows further."""
+    ops.linear_bwd_weight(d, dy, x, gw, gb)
+    if not need_dx:
+        return None
+    dx = torch.empty_like(x)
+    ops.linear_bwd_data(d, dy, w, None, dx)
+    return dx
 
 
 class FusionBlock:
@@ -26,47 +45,33 @@ class FusionBlock:
     def _w(self, ar, name):
         return ar.master(name) if self.fp32_operands else ar.operand(name)
 
-    def _lin(self, x, w, b):
-        f32 = ops.code(torch.float32)
-        d = ops.linear_desc(self._code(), x.shape[0], w.shape[0], x.shape[1], f32, f32)
-        y = torch.empty(x.shape[0], w.shape[0], dtype=torch.float32, device=x.device)
-        ops.linear_fwd(d, x, w, b, None, y)
-        return y, d
-
-    @staticmethod
-    def _lin_bwd(d, dy, x, w, gw, gb):
-        ops.linear_bwd_weight(d, dy, x, gw, gb)
-        dx = torch.empty_like(x)
-        ops.linear_bwd_data(d, dy, w, None, dx)
-        return dx
-
     def forward(self, x, B, M, p_attn, rng, stream_id):
         ar, pre, E = self.bb.arena(), self.pre, x.shape[1]
         xn, st = ops.layernorm_fwd(x, ar.master(f"{pre}.norm1.weight"), ar.master(f"{pre}.norm1.bias"), torch.float32)
         qin = ops.mean_time(xn, B, M, E)
         # nn.MultiheadAttention packs W_q | W_k | W_v as in_proj_weight [3E, E]: row slices of the arena, no copies
         w_in, b_in = self._w(ar, f"{pre}.mha.in_proj_weight"), ar.master(f"{pre}.mha.in_proj_bias")
-        q, d_q = self._lin(qin, w_in[:E], b_in[:E])
-        kv, d_kv = self._lin(xn, w_in[E:], b_in[E:])
+        q, d_q = lin(self._code(), qin, w_in[:E], b_in[:E])
+        kv, d_kv = lin(self._code(), xn, w_in[E:], b_in[E:])
         o = torch.empty(B, E, dtype=torch.float32, device=x.device)
         probs = torch.empty(B, self.heads, M, dtype=torch.float32, device=x.device)
         weights = torch.empty_like(probs)
         ops.fusion_attn_fwd(B, M, E, self.heads, q, kv, o, probs, weights, rng, stream_id, p_attn)
-        y, d_out = self._lin(o, self._w(ar, f"{pre}.mha.out_proj.weight"), ar.master(f"{pre}.mha.out_proj.bias"))
+        y, d_out = lin(self._code(), o, self._w(ar, f"{pre}.mha.out_proj.weight"), ar.master(f"{pre}.mha.out_proj.bias"))
         return y, dict(x=x, st=st, xn=xn, qin=qin, q=q, d_q=d_q, kv=kv, d_kv=d_kv, o=o, probs=probs, weights=weights, d_out=d_out,
                        B=B, M=M, E=E)
 
     def backward(self, sv, dy):
         """dy [B, E] fp32 -> dx [B*M, E]; the block's parameter gradients accumulate into the arena."""
         ar, pre, B, M, E = self.bb.arena(), self.pre, sv["B"], sv["M"], sv["E"]
-        do = self._lin_bwd(sv["d_out"], dy, sv["o"], self._w(ar, f"{pre}.mha.out_proj.weight"), ar.g(f"{pre}.mha.out_proj.weight"),
-                           ar.g(f"{pre}.mha.out_proj.bias"))
+        do = lin_bwd(sv["d_out"], dy, sv["o"], self._w(ar, f"{pre}.mha.out_proj.weight"), ar.g(f"{pre}.mha.out_proj.weight"),
+                     ar.g(f"{pre}.mha.out_proj.bias"))
         dq = torch.empty(B, E, dtype=torch.float32, device=dy.device)
         dkv = torch.empty(B * M, 2 * E, dtype=torch.float32, device=dy.device)
         ops.fusion_attn_bwd(B, M, E, self.heads, sv["q"], sv["kv"], sv["probs"], sv["weights"], do, dq, dkv)
         w_in, gw, gb = self._w(ar, f"{pre}.mha.in_proj_weight"), ar.g(f"{pre}.mha.in_proj_weight"), ar.g(f"{pre}.mha.in_proj_bias")
-        dqin = self._lin_bwd(sv["d_q"], dq, sv["qin"], w_in[:E], gw[:E], gb[:E])
-        dxn = self._lin_bwd(sv["d_kv"], dkv, sv["xn"], w_in[E:], gw[E:], gb[E:])
+        dqin = lin_bwd(sv["d_q"], dq, sv["qin"], w_in[:E], gw[:E], gb[:E])
+        dxn = lin_bwd(sv["d_kv"], dkv, sv["xn"], w_in[E:], gw[E:], gb[E:])
         ops.loc_mean_bwd_add(dqin, dxn.view(B, M, E))  # the query is the mean of the M normalised tokens: dxn += dqin / M
         dx = torch.empty_like(sv["x"])
         ops.layernorm_bwd(dxn, sv["x"], sv["st"], ar.master(f"{pre}.norm1.weight"), dx, False, ar.g(f"{pre}.norm1.weight"),

@@ -29,9 +29,8 @@ masks every step because the seed word advances on the device.
 import torch
 
 from . import ops
-from ._lib import ACT_NONE, ACT_RELU_OUT, EPI_NONE, EPI_RELU, EPI_RESIDUAL
-from .backbone import _join_after_backward
-from .head_engine import FusionBlock
+from ._lib import ACT_RELU_OUT, EPI_NONE, EPI_RELU, EPI_RESIDUAL
+from .head_engine import FusionBlock, lin, lin_bwd
 
 LOC_STREAM_BASE = 0x40000000  # above every Swin / DeepSense stream id ((view * 8 + encoder) * 64 + block) * 8 + site < 2^28)
 SITE_ATTN, SITE_DROP1, SITE_HIDDEN, SITE_DROP2 = range(4)
@@ -58,23 +57,6 @@ class LocFusionStage:
     def stream_id(self, view, layer, site):
         return LOC_STREAM_BASE + ((((view & 0xFFFF) * 8 + self.mi) * 8 + layer) * 8 + site)
 
-    # ------------------------------------------------------------------------------------------------ helpers
-    def _lin(self, x, w, b, rows, n_out, epilogue=EPI_NONE, resid=None, drop=None):
-        f32 = ops.code(torch.float32)
-        d = ops.linear_desc(f32, rows, n_out, x.shape[1], f32, f32, ACT_NONE, epilogue, out_drop=drop)
-        y = torch.empty(rows, n_out, dtype=torch.float32, device=x.device)
-        ops.linear_fwd(d, x, w, b, resid, y)
-        return y, d
-
-    @staticmethod
-    def _lin_bwd(d, dy, x, w, gw, gb, need_dx=True):
-        ops.linear_bwd_weight(d, dy, x, gw, gb)
-        if not need_dx:
-            return None
-        dx = torch.empty_like(x)
-        ops.linear_bwd_data(d, dy, w, None, dx)
-        return dx
-
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, feats, view, training):
         """feats: L fp32 [N, E] features in location order -> (fused [N, E] fp32, saved state for backward)."""
@@ -85,26 +67,26 @@ class LocFusionStage:
         dev = feats[0].device
         p = self.p if training else 0.0
         rng = self.bb.rng_state() if p > 0 else None
-        W = ar.master
+        W, f32 = ar.master, ops.code(torch.float32)
         xs = torch.empty(N, L, E, dtype=torch.float32, device=dev)
         ops.loc_stack([f if f.dtype == torch.float32 and f.is_contiguous() else f.float().contiguous() for f in feats], xs)
         x = xs.view(R, E)
         layers = []
         for li in range(self.blocks):
             pre = f"{self.ctx}.{li}"
-            qkv, d_qkv = self._lin(x, W(f"{pre}.self_attn.in_proj_weight"), W(f"{pre}.self_attn.in_proj_bias"), R, 3 * E)
+            qkv, d_qkv = lin(f32, x, W(f"{pre}.self_attn.in_proj_weight"), W(f"{pre}.self_attn.in_proj_bias"))
             o = torch.empty(R, E, dtype=torch.float32, device=dev)
             probs = torch.empty(N, H, L, L, dtype=torch.float32, device=dev)
             weights = torch.empty_like(probs)
             ops.loc_attn_fwd(N, L, E, H, qkv, o, probs, weights, rng, self.stream_id(view, li, SITE_ATTN), p)
             drop1 = ops.drop_desc(rng, self.stream_id(view, li, SITE_DROP1), p) if p > 0 else None
-            y1, d_o = self._lin(o, W(f"{pre}.self_attn.out_proj.weight"), W(f"{pre}.self_attn.out_proj.bias"), R, E, EPI_RESIDUAL, x, drop1)
+            y1, d_o = lin(f32, o, W(f"{pre}.self_attn.out_proj.weight"), W(f"{pre}.self_attn.out_proj.bias"), EPI_RESIDUAL, x, drop1)
             x1, st1 = ops.layernorm_fwd(y1, W(f"{pre}.norm1.weight"), W(f"{pre}.norm1.bias"), torch.float32)
             F = ar.index[f"{pre}.linear1.weight"][2][0]
-            r, _ = self._lin(x1, W(f"{pre}.linear1.weight"), W(f"{pre}.linear1.bias"), R, F, EPI_RELU)
+            r, _ = lin(f32, x1, W(f"{pre}.linear1.weight"), W(f"{pre}.linear1.bias"), EPI_RELU)
             h = ops.dropout(r, rng, self.stream_id(view, li, SITE_HIDDEN), p) if p > 0 else r
             drop2 = ops.drop_desc(rng, self.stream_id(view, li, SITE_DROP2), p) if p > 0 else None
-            y2, d_2 = self._lin(h, W(f"{pre}.linear2.weight"), W(f"{pre}.linear2.bias"), R, E, EPI_RESIDUAL, x1, drop2)
+            y2, d_2 = lin(f32, h, W(f"{pre}.linear2.weight"), W(f"{pre}.linear2.bias"), EPI_RESIDUAL, x1, drop2)
             x2, st2 = ops.layernorm_fwd(y2, W(f"{pre}.norm2.weight"), W(f"{pre}.norm2.bias"), torch.float32)
             layers.append(dict(x=x, qkv=qkv, d_qkv=d_qkv, o=o, probs=probs, weights=weights, d_o=d_o, y1=y1, st1=st1, x1=x1, h=h, F=F,
                                d_2=d_2, drop2=drop2, y2=y2, st2=st2))
@@ -141,17 +123,17 @@ class LocFusionStage:
             ops.linear_bwd_data(d2, gm, W(f"{pre}.linear2.weight"), s["h"], dh)  # zero where h = 0: relu off or dropped
             dz = ops.dropout(dh, rng, self.stream_id(view, li, SITE_HIDDEN), p) if p > 0 else dh  # x mask: 1 / (1 - p) where kept
             d1 = ops.linear_desc(f32, R, F, E, f32, f32)
-            t = self._lin_bwd(d1, dz, s["x1"], W(f"{pre}.linear1.weight"), G(f"{pre}.linear1.weight"), G(f"{pre}.linear1.bias"))
+            t = lin_bwd(d1, dz, s["x1"], W(f"{pre}.linear1.weight"), G(f"{pre}.linear1.weight"), G(f"{pre}.linear1.bias"))
             ops.axpy(1.0, dy2, t)  # + the residual path around the feed-forward block
             dy1 = torch.empty(R, E, dtype=torch.float32, device=dev)
             ops.layernorm_bwd(t, s["y1"], s["st1"], W(f"{pre}.norm1.weight"), dy1, False, G(f"{pre}.norm1.weight"), G(f"{pre}.norm1.bias"))
             # y1 = x + drop1(o Wout^T + b): the residual-epilogue descriptor masks dy1 in the GEMM loaders
-            do = self._lin_bwd(s["d_o"], dy1, s["o"], W(f"{pre}.self_attn.out_proj.weight"), G(f"{pre}.self_attn.out_proj.weight"),
-                               G(f"{pre}.self_attn.out_proj.bias"))
+            do = lin_bwd(s["d_o"], dy1, s["o"], W(f"{pre}.self_attn.out_proj.weight"), G(f"{pre}.self_attn.out_proj.weight"),
+                         G(f"{pre}.self_attn.out_proj.bias"))
             dqkv = torch.empty(R, 3 * E, dtype=torch.float32, device=dev)
             ops.loc_attn_bwd(N, L, E, H, s["qkv"], s["probs"], s["weights"], do, dqkv)
-            tx = self._lin_bwd(s["d_qkv"], dqkv, s["x"], W(f"{pre}.self_attn.in_proj_weight"), G(f"{pre}.self_attn.in_proj_weight"),
-                               G(f"{pre}.self_attn.in_proj_bias"))
+            tx = lin_bwd(s["d_qkv"], dqkv, s["x"], W(f"{pre}.self_attn.in_proj_weight"), G(f"{pre}.self_attn.in_proj_weight"),
+                         G(f"{pre}.self_attn.in_proj_bias"))
             if li > 0:
                 ops.axpy(1.0, dy1, tx)
                 g = tx
@@ -159,36 +141,3 @@ class LocFusionStage:
                 grads = torch.empty(L, N, E, dtype=torch.float32, device=dev)
                 ops.loc_unstack_add(dy1.view(N, L, E), tx.view(N, L, E), list(grads))
         return list(grads)
-
-
-class LocStageFn(torch.autograd.Function):
-    """One autograd node over a modality's L encoder outputs (they come from L nodes on L streams; autograd hands each its gradient on the
-    stream its forward ran on)."""
-
-    @staticmethod
-    def forward(ctx, engine, view, training, *feats):
-        cur = torch.cuda.current_stream(feats[0].device)
-        for f in feats:  # produced on the encoders' streams: keep their blocks alive for this one
-            f.record_stream(cur)
-        y, saved = engine.forward(list(feats), view, training)
-        ctx.engine, ctx.saved = engine, saved
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        dy = dy.contiguous()
-        dy.record_stream(torch.cuda.current_stream(dy.device))
-        grads = ctx.engine.backward(ctx.saved, dy)
-        ctx.saved = None
-        _join_after_backward(dy.device)  # (see backbone.StageFn.backward)
-        return (None, None, None, *grads)
-
-
-def run_loc_stage(engine, feats, view, training):
-    if torch.is_grad_enabled() and any(f.requires_grad for f in feats):
-        return LocStageFn.apply(engine, view, training, *feats)
-    cur = torch.cuda.current_stream(feats[0].device)
-    for f in feats:
-        f.record_stream(cur)
-    y, _ = engine.forward(list(feats), view, training)
-    return y

@@ -14,7 +14,7 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from focal_amd import runtime  # noqa: E402
-from focal_amd.backbone import HipBackbone, is_hot, is_hot_deepsense_multiloc, run_stage, run_stage_multi  # noqa: E402
+from focal_amd.backbone import HipBackbone, run_stage  # noqa: E402
 from focal_amd.deepsense_engine import DeepSenseModEncoder, DeepSenseMultiLocEncoder  # noqa: E402
 from focal_amd.head_engine import ClassifierHead  # noqa: E402
 from focal_amd.swin_engine import ProjectorHead  # noqa: E402
@@ -37,7 +37,8 @@ class DeepSense(HipBackbone):
         # the global batch normalises over ALL windows.  sync_bn=True all-reduces the per-channel sums (2C floats, twice
         # per BN layer per step) and reproduces that exactly; False = per-rank statistics (throughput mode).
         self.sync_bn = bool(getattr(args, "sync_bn", False)) or os.environ.get("FOCAL_SYNC_BN", "0") == "1"
-        self._init_hip(args)
+        # (pretraining on a multi-location dataset: the second ConvBlock of every modality trains)
+        self._init_hip(args, deepsense_multiloc=self.multi_location_flag)
         self.init_encoder(args)
 
     def init_encoder(self, args):
@@ -50,8 +51,6 @@ class DeepSense(HipBackbone):
             if cfg["loc_out_channels"] != 128 or cfg["loc_mod_out_channels"] != 128:
                 raise NotImplementedError("multi-location DeepSense covers loc_out_channels = loc_mod_out_channels = 128 (64-channel "
                                           f"convolution kernels); got {cfg['loc_out_channels']} / {cfg['loc_mod_out_channels']}")
-            if self._hot is is_hot:  # (pretraining: the second ConvBlock of every modality trains)
-                self._hot = is_hot_deepsense_multiloc
         self.loc_mod_extractors = nn.ModuleDict()
         self.geometry = {}
         for loc in self.locations:
@@ -136,32 +135,23 @@ class DeepSense(HipBackbone):
             self._buffers_by_name["__dev"] = next(self.parameters()).device
         return self._buffers_by_name[name]
 
-    def forward_encoder(self, freq_x, class_head=True, proj_head=False, defer_join=False, view_index=None, views_in_batch=1):
-        if class_head:
-            return self.forward_classifier(freq_x)
+    def _before_fork(self, view_index):
+        if view_index in (None, 0):
+            for enc in self._encoders.values():
+                enc.prepare_packs()  # re-ordered weights for both views' passes: one launch per encoder, before the streams fork
+
+    def _run_encoders(self, freq_x, proj_head, view, dev, cur, point, view_index, views_in_batch):
         loc, locs = self.locations[0], tuple(self.locations)
-        view = self._fwd_calls
-        self._fwd_calls = (self._fwd_calls + 1) & 0xFFFF
-        # one HIP stream per modality encoder (see focal_amd/runtime.py: side streams); joined before returning
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            from focal_amd._lib import FocalHipError
-            raise FocalHipError("the FOCAL HIP path needs the model on a ROCm device (no CPU fallback)")
-        cur = torch.cuda.current_stream(dev)
-        out = {}
         # The two views of a step also get their own streams: the GRU sequence
         # kernels are latency-bound launches of 32 workgroups, and view 2's convolution stack fills the chip under view 1's GRU.
         # BatchNorm's running buffers must see view 1 before view 2: an encoder's pass starts after the previous pass of the same
         # encoder has left its convolution stack (the last BatchNorm), see deepsense_engine.forward.
         # (view_index: FOCAL.forward numbers its two backbone calls 0 / 1; any other caller runs one stream per modality)
         view_streams = view_index is not None and self.training
-        self.arena()  # built (and its bf16 shadow filled) on the caller's stream before any encoder stream forks from it
-        if view_index in (None, 0):
-            for enc in self._encoders.values():
-                enc.prepare_packs()  # re-ordered weights for both views' passes: one launch per encoder, before the streams fork
-        point = runtime.fork_point(dev)  # every encoder starts from here: none waits for the one launched before it
+        pass_args = (view, self.training, view_index if view_streams else None, views_in_batch if self.training else 1)
+        out = {}
         order = list(range(len(self.modalities)))
-        # the heaviest encoder is enqueued first (see SW_Transformer.forward_encoder)
+        # the heaviest encoder is enqueued first (see SW_Transformer._run_encoders)
         order.sort(key=lambda i: -sum(freq_x[l][self.modalities[i]].numel() for l in locs))
         for mi in order:
             mod = self.modalities[mi]
@@ -169,18 +159,13 @@ class DeepSense(HipBackbone):
             # wait for the view-1 pass that was enqueued there
             st = runtime.fork_from(dev, (view_index * len(self.modalities) + 1 if view_streams else 0) + mi, point)
             with torch.cuda.stream(st):
-                enc = self._encoders[(locs if self.multi_location_flag else loc, mod)]
-                enc.pass_order = view_index if view_streams else None
-                enc.views_in_batch = views_in_batch if self.training else 1
                 if self.multi_location_flag:  # the modality's L spectra, in location order, into one node
-                    f = run_stage_multi(self, enc, [freq_x[l][mod] for l in locs], view, self.training)
+                    f = run_stage(self, self._encoders[(locs, mod)], [freq_x[l][mod] for l in locs], *pass_args)
                 else:
-                    f = run_stage(self, enc, freq_x[loc][mod], view, self.training)
+                    f = run_stage(self, self._encoders[(loc, mod)], freq_x[loc][mod], *pass_args)
                 out[mod] = run_stage(self, self._heads[mod], f) if proj_head else f
                 out[mod].record_stream(cur)
-        if not defer_join:  # FOCAL.forward joins once after both views so that their encoders overlap
-            runtime.join_all(dev)
-        return {mod: out[mod] for mod in self.modalities}
+        return out
 
     def finish_views(self):
         """After both views' passes of a step (FOCAL.forward): the BatchNorm running-buffer updates the passes recorded (see
@@ -189,20 +174,5 @@ class DeepSense(HipBackbone):
         for enc in self._encoders.values():
             enc.finish_views(dev)
 
-    def forward_classifier(self, freq_x):
-        """`backbone(freq_x, class_head=True)` -> logits (reference: models/DeepSense.py:154-157).  This is the finetuning path: the encoders in front run
-        forward-only (finetuning freezes them, general_utils/weight_utils.py:61-80), the head -- the class layer on the concatenated features -- is one
-        differentiable node (focal_amd/head_engine.py)."""
-        if self._hot.__name__ in ("is_hot", "is_hot_deepsense_multiloc"):
-            raise NotImplementedError("class_head=True needs the classifier head in the parameter arena: build the model with "
-                                      "args.stage = 'finetune' (or supervised train_mode)")
-        if self.supervised:  # supervised training from scratch (train_utils/supervised_train.py): the gradient flows on into the encoders
-            feats = self.forward_encoder(freq_x, class_head=False, proj_head=False)
-        else:
-            with torch.no_grad():
-                feats = self.forward_encoder(freq_x, class_head=False, proj_head=False)
-        x = torch.cat([feats[m] for m in self.modalities], dim=1)
-        return run_stage(self, self._class_head, x, self.training)
-
-    def forward(self, freq_x, class_head=True, proj_head=False, defer_join=False, view_index=None, views_in_batch=1):
-        return self.forward_encoder(freq_x, class_head, proj_head, defer_join, view_index, views_in_batch)
+    def _join_features(self, feats):
+        return torch.cat(feats, dim=1)  # (reference: models/DeepSense.py:154-157, the class layer reads the concatenated features)

@@ -1,5 +1,4 @@
 """FOCAL framework wrapper (reference: models/FOCALModules.py): the backbone is run on both augmented views."""
-import inspect
 import os
 import sys
 
@@ -9,6 +8,8 @@ import torch.nn as nn
 _ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..", ".."))
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
+
+from focal_amd import runtime  # noqa: E402
 
 
 class FOCAL(nn.Module):
@@ -24,28 +25,21 @@ class FOCAL(nn.Module):
         # two backbone calls in program order, as in the reference (:21-34): BatchNorm statistics are per view and the
         # running buffers see view 1 before view 2.  HIP backbones run each modality encoder on its own stream; the
         # streams are joined once here, after both views, so late (small) stages of the two views overlap.
-        if getattr(self.backbone, "views_share_pass", False):
+        if self.backbone.views_share_pass:
             # A backbone without batch statistics (SW_Transformer: LayerNorm only) gives the same features whether the two
             # views are two batches or one batch of 2B; one pass halves the launch count and doubles every kernel's size.
             # DeepSense's BatchNorms compute per-view statistics inside the one batch (views_in_batch).
             both = {loc: {mod: _as_one_batch(x, aug_freq_input2[loc][mod]) for mod, x in mods.items()}
                     for loc, mods in aug_freq_input1.items()}
             # (a backbone with batch statistics -- DeepSense -- is told that the batch is two views: its BatchNorms keep them apart)
-            kw = {"views_in_batch": 2} if "views_in_batch" in inspect.signature(self.backbone.forward).parameters else {}
-            feats = self.backbone(both, class_head=False, proj_head=proj_head, **kw)
+            feats = self.backbone(both, class_head=False, proj_head=proj_head, views_in_batch=2)
             halves = {m: _SplitHalves.apply(f) for m, f in feats.items()}
             return {m: h[0] for m, h in halves.items()}, {m: h[1] for m, h in halves.items()}
-        kw = {}
-        if "defer_join" in inspect.signature(self.backbone.forward).parameters:
-            kw["defer_join"] = True
-        views = "view_index" in inspect.signature(self.backbone.forward).parameters  # the two passes may overlap on separate streams
-        mod_features1 = self.backbone(aug_freq_input1, class_head=False, proj_head=proj_head, **kw, **({"view_index": 0} if views else {}))
-        mod_features2 = self.backbone(aug_freq_input2, class_head=False, proj_head=proj_head, **kw, **({"view_index": 1} if views else {}))
-        if kw:
-            from focal_amd import runtime
-            runtime.join_all(next(self.backbone.parameters()).device)
-        if hasattr(self.backbone, "finish_views"):
-            self.backbone.finish_views()
+        # (view_index: the two passes may overlap on separate streams)
+        mod_features1 = self.backbone(aug_freq_input1, class_head=False, proj_head=proj_head, defer_join=True, view_index=0)
+        mod_features2 = self.backbone(aug_freq_input2, class_head=False, proj_head=proj_head, defer_join=True, view_index=1)
+        runtime.join_all(next(self.backbone.parameters()).device)
+        self.backbone.finish_views()
         return mod_features1, mod_features2
 
 

@@ -22,7 +22,7 @@ if _ROOT not in sys.path:
 from focal_amd import runtime  # noqa: E402
 from focal_amd.backbone import HipBackbone, run_stage  # noqa: E402
 from focal_amd.head_engine import ClassifierHead  # noqa: E402
-from focal_amd.loc_engine import LocFusionStage, run_loc_stage  # noqa: E402
+from focal_amd.loc_engine import LocFusionStage  # noqa: E402
 from focal_amd.swin_engine import ProjectorHead, SwinModEncoder  # noqa: E402
 from input_utils.padding_utils import get_padded_size  # noqa: E402
 from models.FusionModules import LocContextLayer, TransformerFusionBlock  # noqa: E402
@@ -137,24 +137,10 @@ class SW_Transformer(HipBackbone):
         self._heads = {mod: ProjectorHead(self, mod) for mod in self.modalities}
         self._class_head = ClassifierHead(self, "mod_fusion_layers", cfg["loc_head_num"], cfg["dropout_ratio"])
 
-    def forward_encoder(self, freq_x, class_head=True, proj_head=False, defer_join=False):
-        if class_head:
-            return self.forward_classifier(freq_x)
+    def _run_encoders(self, freq_x, proj_head, view, dev, cur, point, view_index, views_in_batch):
+        """(view_index, views_in_batch: no batch statistics here, the two views are two batches or one batch of 2B alike)"""
         loc = self.locations[0]
-        view = self._fwd_calls
-        self._fwd_calls = (self._fwd_calls + 1) & 0xFFFF
-        # one HIP stream per modality encoder (see focal_amd/runtime.py: side streams); joined before returning
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            from focal_amd._lib import FocalHipError
-            raise FocalHipError("the FOCAL HIP path needs the model on a ROCm device (no CPU fallback)")
-        cur = torch.cuda.current_stream(dev)
         out = {}
-        # The parameter arena (and its bf16 shadow) must exist BEFORE the fork point: built lazily inside the first encoder's pass it was
-        # filled on that encoder's stream AFTER the point the other encoders start from, and on a fresh model they could read a zero arena
-        # (round 5: test_train_step_loss_and_gradients[bf16] saw an all-zero seismic embedding in 2 of 16 fresh processes).
-        self.arena()
-        point = runtime.fork_point(dev)  # every encoder starts from here: none waits for the one launched before it
         # The heaviest modality is enqueued first: the order of enqueueing is the order of the nodes in the captured step, and what the
         # runtime dispatches first gets a head start on the stream that ends the step (audio has 2/3 of the MOD step's work).  Autograd
         # then reaches the heaviest encoder's backward pass last; that order was measured not to matter.  +1.4 % on the step
@@ -176,9 +162,7 @@ class SW_Transformer(HipBackbone):
                 f = run_stage(self, self._encoders[(loc, mod)], freq_x[loc][mod], view, self.training)
                 out[mod] = run_stage(self, self._heads[mod], f) if proj_head else f
                 out[mod].record_stream(cur)
-        if not defer_join:  # FOCAL.forward joins once after both views so that their encoders overlap
-            runtime.join_all(dev)
-        return {mod: out[mod] for mod in self.modalities}
+        return out
 
     def _forward_locations(self, freq_x, proj_head, view, dev, cur, point, order, out):
         """Multi-location dataset: the L*M encoders fork from one point, each on its own stream; a modality's location fusion waits for
@@ -195,23 +179,8 @@ class SW_Transformer(HipBackbone):
                     feats.append(run_stage(self, self._encoders[(loc, mod)], freq_x[loc][mod], view, self.training))
                 if st != cur:
                     cur.wait_stream(st)  # (an event on st now: that stream carries this one encoder)
-            f = run_loc_stage(self._loc_stages[mod], feats, view, self.training)
+            f = run_stage(self, self._loc_stages[mod], feats, view, self.training, input_grads=True)
             out[mod] = run_stage(self, self._heads[mod], f) if proj_head else f
 
-    def forward_classifier(self, freq_x):
-        """`backbone(freq_x, class_head=True)` -> logits (reference: models/SW_Transformer.py:269-276).  This is the finetuning path: the encoders in front run
-        forward-only (finetuning freezes them, general_utils/weight_utils.py:61-80), the head -- modality fusion + class layer -- is one
-        differentiable node (focal_amd/head_engine.py)."""
-        if self._hot.__name__ in ("is_hot", "is_hot_ape"):
-            raise NotImplementedError("class_head=True needs the classifier head in the parameter arena: build the model with "
-                                      "args.stage = 'finetune' (or supervised train_mode)")
-        if self.supervised:  # supervised training from scratch (train_utils/supervised_train.py): the gradient flows on into the encoders
-            feats = self.forward_encoder(freq_x, class_head=False, proj_head=False)
-        else:
-            with torch.no_grad():
-                feats = self.forward_encoder(freq_x, class_head=False, proj_head=False)
-        x = torch.stack([feats[m] for m in self.modalities], dim=1)  # [b, M, c] (the reference's [b, 1, M, c] with i = 1)
-        return run_stage(self, self._class_head, x, self.training)
-
-    def forward(self, freq_x, class_head=True, proj_head=False, defer_join=False):
-        return self.forward_encoder(freq_x, class_head, proj_head, defer_join)
+    def _join_features(self, feats):
+        return torch.stack(feats, dim=1)  # [b, M, c] (the reference's [b, 1, M, c] with i = 1) for the modality fusion block

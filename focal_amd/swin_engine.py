@@ -16,7 +16,7 @@ from typing import NamedTuple
 import torch
 
 from . import ops
-from ._lib import ACT_GELU, ACT_NONE, EPI_GELU, EPI_NONE, EPI_RESIDUAL
+from ._lib import ACT_GELU, ACT_NONE, ACT_RELU_OUT, EPI_GELU, EPI_NONE, EPI_RELU, EPI_RESIDUAL
 
 
 def tail_fp32(bb, which="mod_in"):
@@ -517,7 +517,6 @@ class ProjectorHead:
         cc = f32 if tail_fp32(bb, "projector") else ops.code(bb.compute_dtype)   # (fp32 operands in bf16 mode too: tail_fp32)
         B, K = feat.shape
         E = ar.index[f"{self.pre}.0.weight"][2][0]
-        from ._lib import ACT_RELU_OUT, EPI_RELU
         d0 = ops.linear_desc(cc, B, E, K, f32, f32, ACT_NONE, EPI_RELU)
         h = torch.empty(B, E, dtype=torch.float32, device=feat.device)
         ops.linear_fwd(d0, feat, tail_weight(bb, ar, f"{self.pre}.0.weight", "projector"), ar.master(f"{self.pre}.0.bias"), None, h)

@@ -65,13 +65,21 @@ def test_har3loc_with_ape_puts_every_location_table_into_the_hot_set():
 
 
 def test_ape_off_leaves_the_arena_layout_alone():
+    """APE off: the pretraining and the supervised arena are what the rules without the switch gave -- restated here as prefix tuples, and
+    as the layouts recorded at the commit before the rule became one object (tests/golden/arena_layouts_parent.json)."""
+    import hashlib
     from focal_amd.arena import layout
-    from focal_amd.backbone import is_hot, is_hot_supervised
-    _, net = _net(ape=False)
-    assert net._hot is is_hot
-    assert layout(net, net._hot) == layout(net, is_hot)
-    _, sup = _net(ape=False, train_mode="supervised")
-    assert sup._hot is is_hot_supervised
+    parent = json.load(open(os.path.join(GOLD, "arena_layouts_parent.json")))["cases"]
+    pretrain_dead = ("patch_embed.", "class_layer.", "mod_fusion_layers.", APE, "mod_extractors.", "loc_fusion_layers.")
+    supervised_dead = (APE, "mod_extractors.", "loc_fusion_layers.", "loc_context_layers.", "loc_fusion_layer.", "mod_projectors.")
+    for kw, dead, case in ((dict(), pretrain_dead, "MOD/SW_Transformer/pretrain/ape_off"),
+                           (dict(train_mode="supervised"), supervised_dead, "MOD/SW_Transformer/supervised/ape_off")):
+        _, net = _net(ape=False, **kw)
+        assert layout(net, net._hot) == layout(net, lambda n: not n.startswith(dead))
+        index, total = layout(net, net._hot)
+        rows = [[n, off, numel, list(shape)] for n, (off, numel, shape) in index.items()]
+        assert (len(rows), total) == (parent[case]["hot"], parent[case]["total"])
+        assert hashlib.sha256(json.dumps(rows).encode()).hexdigest() == parent[case]["sha256"]
 
 
 def test_finetune_keeps_the_position_embedding_frozen():

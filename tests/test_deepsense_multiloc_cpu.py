@@ -4,6 +4,7 @@ reference-layout state dict loads, the second ConvBlocks (mod_extractors.*) are 
 path and other channel counts are refused, the two new entry points are declared, and no two dropout sites of a step share a stream."""
 import argparse
 import copy
+import hashlib
 import json
 import os
 import re
@@ -83,8 +84,9 @@ def test_har3loc_second_conv_blocks_are_hot_in_pretraining(net3):
     order = [n for n, *_ in _layout(net3, net3._hot)]
     hot = set(order)
     assert set(second) <= hot
-    from focal_amd.backbone import is_hot
-    assert hot - set(second) == {n for n, _ in net3.named_parameters() if is_hot(n)}
+    # ... and besides them exactly the single-location hot set, restated: the patch embedding, the head and the mean fusion stay out
+    pretrain_dead = ("patch_embed.", "class_layer.", "mod_fusion_layers.", "absolute_pos_embed.", "mod_extractors.", "loc_fusion_layers.")
+    assert hot - set(second) == {n for n, _ in net3.named_parameters() if not n.startswith(pretrain_dead)}
     assert not any(n.startswith("class_layer.") for n in hot)
     # the arena keeps the module order: the second blocks between the first-level blocks and the GRUs, as in the state dict
     assert order == [n for n, _ in net3.named_parameters() if n in hot]
@@ -94,10 +96,13 @@ def test_har3loc_second_conv_blocks_are_hot_in_pretraining(net3):
 
 
 def test_mod_keeps_its_hot_set_and_arena_layout():
-    from focal_amd.backbone import is_hot
     net = _net("MOD")
-    assert net._hot is is_hot
+    # the rule is the single-location one: the layout it gives is the restated one, and the parent's recorded one
     assert _layout(net, net._hot) == _single_location_layout(net)
+    assert {n for n, _ in net.named_parameters() if net._hot(n)} == {n for n, _ in net.named_parameters() if not n.startswith(SINGLE_LOCATION_DEAD)}
+    rows = [[n, off, numel, list(shape)] for n, off, numel, shape in _layout(net, net._hot)]
+    parent = json.load(open(os.path.join(GOLD, "arena_layouts_parent.json")))["cases"]["MOD/DeepSense/pretrain"]
+    assert hashlib.sha256(json.dumps(rows).encode()).hexdigest() == parent["sha256"] and len(rows) == parent["hot"]
     assert not any(n.startswith("mod_extractors.") for n, *_ in _layout(net, net._hot))
 
 

@@ -117,7 +117,7 @@ def _torch_reference(net, feats, dy):
 @pytest.mark.parametrize("blocks", [1, 2])
 def test_loc_stage_against_torch_encoder_layer(ct, blocks):
     """loc_block_num encoder layers + the fusion block at N = 512, L = 3: output, input gradient and every parameter gradient."""
-    from focal_amd.loc_engine import run_loc_stage
+    from focal_amd.backbone import run_stage
     from oracle.weights import fill_state_dict_
     N, L, E = 512, 3, 256
     net = _LocOnly.build(L, E, 4, blocks, 0.0, ct)
@@ -127,7 +127,7 @@ def test_loc_stage_against_torch_encoder_layer(ct, blocks):
     feats = [torch.randn(N, E, generator=g).cuda().requires_grad_(True) for _ in range(L)]
     dy = torch.randn(N, E, generator=g).cuda()
     net.arena().zero_grad()
-    y = run_loc_stage(net.stage, feats, 0, True)
+    y = run_stage(net, net.stage, feats, 0, True, input_grads=True)
     y.backward(dy)
     torch.cuda.synchronize()
     ref_y, ref_dx, ref_g = _torch_reference(net, feats, dy)
