@@ -146,6 +146,14 @@ class GRUDesc(C.Structure):
     _fields_ = [("B", C.c_int), ("T", C.c_int), ("H", C.c_int), ("whh_frag", C.c_int)]
 
 
+class KnnDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("nq", "nt", "D", "k", "n_classes", "slices")]
+
+
+# focal_knn_search: query rows per workgroup, training rows per tile, and the kernel's limits (include/focal_hip.h)
+KNN_QUERY_TILE, KNN_TRAIN_TILE, KNN_MAX_K, KNN_MAX_CLASSES = 128, 64, 16, 64
+
+
 class AdamWDesc(C.Structure):
     _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("l2_decay", C.c_int)]
 
@@ -232,6 +240,8 @@ PROTOTYPES = {
     "focal_loc_mean_bwd_add": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P]),
     "focal_cross_entropy": (C.c_int, [C.c_int, C.c_int, P, P, P, P, P]),
     "focal_eval_accumulate": (C.c_int, [C.c_int, C.c_int, P, P, P, P, P, P, P]),
+    "focal_knn_search": (C.c_int, [C.POINTER(KnnDesc), P, P, P, P, P, P]),
+    "focal_knn_vote": (C.c_int, [C.POINTER(KnnDesc), P, P, P, P, P, P, P, P, P]),
     "focal_small_linear_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P]),
     "focal_small_linear_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "focal_loss_head_workspace": (C.c_size_t, [C.POINTER(LossDesc)]),

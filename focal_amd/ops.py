@@ -1339,6 +1339,63 @@ class EvalState:
         return float(loss_sum), int(n_batches), words[4:4 + cells].astype("int64").reshape(self.C, self.C)
 
 
+def knn_check_limits(D, k, n_classes):
+    """The limits of focal_knn_search / focal_knn_vote on the feature width, k and the class count, refused here with the limit named
+    (the library refuses them too, before any launch)."""
+    if not 1 <= k <= _lib.KNN_MAX_K:
+        raise _lib.FocalHipError(f"knn: need 1 <= k <= {_lib.KNN_MAX_K} (got k={k})")
+    if not 1 <= n_classes <= _lib.KNN_MAX_CLASSES:
+        raise _lib.FocalHipError(f"knn: need 1 <= n_classes <= {_lib.KNN_MAX_CLASSES} (got n_classes={n_classes})")
+    if D < 4 or D % 4:
+        raise _lib.FocalHipError(f"knn: need a feature width D >= 4 with D % 4 == 0 (got D={D})")
+
+
+def knn_default_slices(nq, nt, device):
+    """Slices of the training rows so that the search launches about two workgroups per CU, never more than there are training tiles."""
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    q_tiles = -(-nq // _lib.KNN_QUERY_TILE)
+    return max(1, min(-(-nt // _lib.KNN_TRAIN_TILE), round(2 * cus / q_tiles)))
+
+
+def knn_search_vote(q, t, t_sq, t_labels, k, n_classes, q_labels=None, conf=None, want_neighbours=False, slices=None):
+    """The k nearest rows of t (fp32 [nt, D], squared norms t_sq [nt], labels t_labels int64 [nt]) for every row of q (fp32 [nq, D]) and
+    their vote (focal_knn_search + focal_knn_vote: two launches, no host read).  Returns preds (int64 [nq]) and, with want_neighbours,
+    also nbr_idx (int32 [nq, k]) and nbr_d2 (fp32 [nq, k]), sorted by (d2, index); columns from min(k, nt) on hold -1 / +inf.  conf
+    (int32 [C*C + 1], with q_labels) accumulates the confusion matrix as eval_accumulate's prediction mode does.  The results do not
+    depend on `slices` (None: knn_default_slices)."""
+    _need_cuda(q, t, t_sq, t_labels, q_labels, conf)
+    if q.dtype != torch.float32 or t.dtype != torch.float32 or t_sq.dtype != torch.float32 or q.dim() != 2 or t.dim() != 2:
+        raise _lib.FocalHipError("knn_search_vote: q, t and t_sq are fp32, q and t matrices")
+    nq, D = q.shape
+    nt = t.shape[0]
+    if t.shape[1] != D or t_sq.numel() != nt or t_labels.dtype != torch.int64 or t_labels.numel() != nt:
+        raise _lib.FocalHipError(f"knn_search_vote: q {tuple(q.shape)} against t {tuple(t.shape)}, {t_sq.numel()} norms and "
+                                 f"{t_labels.numel()} int64 labels")
+    if nq < 1 or nt < 1:
+        raise _lib.FocalHipError(f"knn_search_vote: need nq >= 1 and nt >= 1 (got nq={nq} nt={nt})")
+    k, n_classes = int(k), int(n_classes)
+    knn_check_limits(D, k, n_classes)
+    if conf is not None:
+        if conf.dtype != torch.int32 or conf.numel() != n_classes * n_classes + 1:
+            raise _lib.FocalHipError(f"knn_search_vote: conf must be int32 [{n_classes * n_classes + 1}]")
+        if q_labels is None or q_labels.dtype != torch.int64 or q_labels.numel() != nq:
+            raise _lib.FocalHipError("knn_search_vote: a confusion matrix needs q_labels int64 [nq]")
+    slices = knn_default_slices(nq, nt, q.device) if slices is None else int(slices)
+    if slices < 1:
+        raise _lib.FocalHipError(f"knn_search_vote: need slices >= 1 (got {slices})")
+    d = _lib.KnnDesc(nq, nt, D, k, n_classes, slices)
+    lib = _lib.load()
+    part_d2 = torch.empty(nq, slices, k, dtype=torch.float32, device=q.device)
+    part_idx = torch.empty(nq, slices, k, dtype=torch.int32, device=q.device)
+    check(lib.focal_knn_search(C.byref(d), _p(q), _p(t), _p(t_sq), _p(part_d2), _p(part_idx), _stream()))
+    preds = torch.empty(nq, dtype=torch.int64, device=q.device)
+    nbr_idx = torch.empty(nq, k, dtype=torch.int32, device=q.device) if want_neighbours else None
+    nbr_d2 = torch.empty(nq, k, dtype=torch.float32, device=q.device) if want_neighbours else None
+    check(lib.focal_knn_vote(C.byref(d), _p(part_d2), _p(part_idx), _p(t_labels), _p(q_labels), _p(preds), _p(nbr_idx), _p(nbr_d2),
+                             _p(conf), _stream()))
+    return (preds, nbr_idx, nbr_d2) if want_neighbours else preds
+
+
 def mean_time(x, B, T, D):
     y = torch.empty(B, D, dtype=torch.float32, device=x.device)
     check(_lib.load().focal_mean_time(B, T, D, _p(x), _p(y), _stream()))

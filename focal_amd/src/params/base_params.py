@@ -24,6 +24,7 @@ def parse_base_args(option="train"):
     p.add_argument("-init_weight", type=str, default=None, help="[build extension] backbone state dict to start pretraining from.")
     p.add_argument("-config", type=str, default=None, help="[build extension] dataset YAML to use instead of ./data/{dataset}.yaml.")
     p.add_argument("-sync_bn", action="store_true", help="[build extension] DeepSense under torchrun: cross-rank BatchNorm statistics.")
+    p.add_argument("-knn_k", type=int, default=5, help="[build extension] eval_knn.py: neighbours of the KNN estimator (the reference fits sklearn's default, 5).")
     args = p.parse_args()
     args.option = option
     return args

@@ -54,6 +54,25 @@ class GpuKNNClassifier:
             out.append(votes.argmax(1))  # first maximum = smallest label among tied classes
         return torch.cat(out)
 
+    @torch.no_grad()
+    def predict_fused(self, features, labels=None, state=None, want_neighbours=False):
+        """`predict` without the [queries, training rows] distance matrix: the search keeps each query's k best inside the product's
+        epilogue and a second launch votes (ops.knn_search_vote).  With `state` (an ops.EvalState) and `labels`, the confusion matrix
+        of the predictions is added to the state's on the device.  Returns the predictions, with want_neighbours also the sorted
+        neighbour indices [nq, k] and squared distances.  Raises FocalHipError, naming the limit, for a feature width or a class count
+        the kernel does not take."""
+        q = features.detach().float().contiguous()
+        n_classes = self.n_classes if state is None else state.C
+        ops.knn_check_limits(q.shape[1], self.k, max(n_classes, self.n_classes))
+        conf = q_labels = None
+        if state is not None:
+            if labels is None:
+                raise ValueError("predict_fused: accumulating into a state needs the queries' labels")
+            labels = labels.argmax(dim=1) if labels.dim() > 1 else labels
+            conf, q_labels = state.conf, labels.detach().to(q.device).long().contiguous()
+        return ops.knn_search_vote(q, self.x, self.x_sq, self.y, self.k, n_classes, q_labels=q_labels, conf=conf,
+                                   want_neighbours=want_neighbours)
+
 
 def compute_knn(args, classifier, augmenter, data_loader_train):
     """Fit the estimator on the training set's features (reference :22-42)."""

@@ -674,6 +674,26 @@ int focal_cross_entropy(int B, int C, const float* logits, const long* labels, f
  * be ordered by their stream. */
 int focal_eval_accumulate(int B, int C, const float* logits, const long* preds_in, const long* labels, double* acc, int* conf,
                           long* preds_out, void* stream);
+/* KNN scoring of un-projected backbone features (train_utils/knn.py: GpuKNNClassifier.predict_fused, src/eval_knn.py): the k nearest
+ * training rows of every query under d2 = (|q|^2 + |t|^2) - 2 q.t in exact fp32 (v_mfma_f32_16x16x4_f32), ordered by (d2, training
+ * index); a NaN distance orders behind every number.  Two launches, no allocation and no host read: both can be captured.
+ * focal_knn_search: q fp32 [nq, D], t fp32 [nt, D], t_sq fp32 [nt] = the rows' squared norms (|q|^2 is taken in the kernel).  The
+ * training rows are cut into `slices` contiguous slices of ceil(nt / slices) rows; a workgroup owns 128 queries and one slice and
+ * writes that slice's k best per query to part_d2 / part_idx, each [nq, slices, k], ascending; slots beyond the slice's row count
+ * carry +inf and index -1.  d2 of a pair depends on the two rows alone -- not on the row's place in t, the tile or `slices` -- so the
+ * outputs of focal_knn_vote are bit-identical for every `slices`, and duplicate training rows tie exactly (the smaller index wins).
+ * focal_knn_vote: merges the slices into the k_eff = min(k, nt) neighbours of each query; preds [nq] = the most frequent of their
+ * t_labels, ties to the smallest label (sklearn's mode).  nbr_idx / nbr_d2 ([nq, k] or NULL) receive the sorted lists, columns from
+ * k_eff on -1 / +inf.  conf (int [C*C + 1] or NULL, needs q_labels [nq]) += the confusion matrix, with the semantics of
+ * focal_eval_accumulate's prediction mode (a row whose label or prediction is outside [0, C) adds 1 to conf[C*C] and nothing else),
+ * by integer atomics: calls that share conf need no ordering beyond the stream's.
+ * Limits (FOCAL_EINVAL before any launch): 1 <= k <= 16, 1 <= n_classes <= 64, D >= 4, D % 4 == 0, nt, nq, slices >= 1, q and t
+ * 16-byte aligned. */
+typedef struct { int nq, nt, D, k, n_classes, slices; } focal_knn_desc;
+int focal_knn_search(const focal_knn_desc* d, const float* q, const float* t, const float* t_sq, float* part_d2, int* part_idx,
+                     void* stream);
+int focal_knn_vote(const focal_knn_desc* d, const float* part_d2, const int* part_idx, const long* t_labels, const long* q_labels,
+                   long* preds, int* nbr_idx, float* nbr_d2, int* conf, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ location fusion (SW_Transformer)
  * Multi-location datasets: per modality, the L location features of a sample are a sequence of L tokens that runs through
