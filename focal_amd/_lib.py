@@ -154,6 +154,14 @@ class KnnDesc(C.Structure):
 KNN_QUERY_TILE, KNN_TRAIN_TILE, KNN_MAX_K, KNN_MAX_CLASSES = 128, 64, 16, 64
 
 
+class KMeansDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n", "D", "K", "R", "slices")]
+
+
+# focal_kmeans_assign / focal_kmeans_update: the limits on the clusters per restart and on all restarts' centroids (include/focal_hip.h)
+KMEANS_MAX_K, KMEANS_MAX_CENTROIDS = 64, 1024
+
+
 class AdamWDesc(C.Structure):
     _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("l2_decay", C.c_int)]
 
@@ -242,6 +250,9 @@ PROTOTYPES = {
     "focal_eval_accumulate": (C.c_int, [C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "focal_knn_search": (C.c_int, [C.POINTER(KnnDesc), P, P, P, P, P, P]),
     "focal_knn_vote": (C.c_int, [C.POINTER(KnnDesc), P, P, P, P, P, P, P, P, P]),
+    "focal_kmeans_assign": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P]),
+    "focal_kmeans_update_workspace": (C.c_size_t, [C.POINTER(KMeansDesc)]),
+    "focal_kmeans_update": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P, P, C.c_size_t, P]),
     "focal_small_linear_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P]),
     "focal_small_linear_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "focal_loss_head_workspace": (C.c_size_t, [C.POINTER(LossDesc)]),

@@ -10,22 +10,10 @@
 // tree, |t|^2 passed in -- whatever tile, lane or slice the pair falls into: the result is bit-identical for every `slices`.
 // focal_knn_vote: one thread per query merges the `slices` lists under the same order, votes (most frequent label, ties to the smallest)
 // and optionally writes the neighbour lists and adds to a confusion matrix laid out as focal_eval_accumulate's.
-#include "gemm.hpp"
+#include "knn_dist.hpp"
 
 #define KNN_MAX_K 16
 #define KNN_MAX_C 64
-constexpr int KNN_BQ = 128, KNN_BT = 64, KNN_BK = 32;
-constexpr unsigned long long KNN_EMPTY = ~0ull;
-
-__device__ __forceinline__ uint32_t knn_key(float d) {
-  if (d != d) return 0xFFFFFFFFu;
-  const uint32_t u = __float_as_uint(d + 0.0f);  // (-0 -> +0)
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float knn_unkey(uint32_t k) {
-  if (k == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
 
 // The KC best entries seen, ascending, in registers: every index below is a compile-time constant.
 template <int KC> struct KnnBest {
@@ -70,23 +58,7 @@ __global__ __launch_bounds__(256) void knn_search_kernel(const focal_knn_desc d,
   const int q_ext = d.nq - q0;
   const float* qb = q + (long)q0 * D;
 
-  // |q|^2: 8 lanes per row, each a k-ordered fma chain over its 16-byte chunks, joined by a fixed xor tree -- the same for every row
-#pragma unroll
-  for (int pass = 0; pass < KNN_BQ / 32; ++pass) {
-    const int row = pass * 32 + (tid >> 3), part = tid & 7;
-    float sum = 0.f;
-    if (row < q_ext) {
-      const float4* src = reinterpret_cast<const float4*>(qb + (long)row * D);
-      for (int c = part; c < D / 4; c += 8) {
-        const float4 v = src[c];
-        sum = fmaf(v.x, v.x, sum); sum = fmaf(v.y, v.y, sum); sum = fmaf(v.z, v.z, sum); sum = fmaf(v.w, v.w, sum);
-      }
-    }
-    sum += __shfl_xor(sum, 1, 64);
-    sum += __shfl_xor(sum, 2, 64);
-    sum += __shfl_xor(sum, 4, 64);
-    if (part == 0) qsq_s[row] = sum;
-  }
+  knn_row_norms(qb, D, q_ext, tid, qsq_s);
 
   KnnBest<KC> best;
   best.init();

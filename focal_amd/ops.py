@@ -1396,6 +1396,101 @@ def knn_search_vote(q, t, t_sq, t_labels, k, n_classes, q_labels=None, conf=None
     return (preds, nbr_idx, nbr_d2) if want_neighbours else preds
 
 
+def kmeans_check_limits(D, K, R):
+    """The limits of focal_kmeans_assign / focal_kmeans_update on the feature width, the clusters per restart and the restarts, refused
+    here with the limit named (the library refuses them too, before any launch)."""
+    if D < 4 or D % 4:
+        raise _lib.FocalHipError(f"kmeans: need a feature width D >= 4 with D % 4 == 0 (got D={D})")
+    if not 1 <= K <= _lib.KMEANS_MAX_K:
+        raise _lib.FocalHipError(f"kmeans: need 1 <= K <= {_lib.KMEANS_MAX_K} (got K={K})")
+    if R < 1 or R * K > _lib.KMEANS_MAX_CENTROIDS:
+        raise _lib.FocalHipError(f"kmeans: need R >= 1 and R * K <= {_lib.KMEANS_MAX_CENTROIDS} (got R={R} K={K})")
+
+
+def kmeans_default_slices(n, D, device):
+    """Row slices of focal_kmeans_update: knn_default_slices' rule (about two workgroups per CU) with the update's 64-column chunks in the
+    place of the query tiles, never more than there are 64-row blocks."""
+    return knn_default_slices(-(-D // 64) * _lib.KNN_QUERY_TILE, n, device)
+
+
+def _kmeans_args(who, x, c, c_sq, K):
+    _need_cuda(x, c, c_sq)
+    if x.dtype != torch.float32 or c.dtype != torch.float32 or c_sq.dtype != torch.float32 or x.dim() != 2 or c.dim() != 2:
+        raise _lib.FocalHipError(f"{who}: x, c and c_sq are fp32, x and c matrices")
+    if not (x.is_contiguous() and c.is_contiguous() and c_sq.is_contiguous()):
+        raise _lib.FocalHipError(f"{who}: x, c and c_sq must be contiguous")
+    n, D = x.shape
+    K = int(K)
+    if K < 1 or c.shape[0] % K or c.shape[1] != D or c_sq.numel() != c.shape[0]:
+        raise _lib.FocalHipError(f"{who}: x {tuple(x.shape)} against c {tuple(c.shape)}, {c_sq.numel()} norms and K={K} "
+                                 f"(need 1 <= K <= {_lib.KMEANS_MAX_K} and c [R * K, D])")
+    R = c.shape[0] // K
+    if n < 1:
+        raise _lib.FocalHipError(f"{who}: need n >= 1 (got n={n})")
+    kmeans_check_limits(D, K, R)
+    return n, D, K, R
+
+
+def kmeans_assign(x, c, c_sq, K, labels=None, min_d2=None, changed=None, want_min_d2=False):
+    """labels[r, i] = the nearest of restart r's K centroids (c fp32 [R * K, D], squared norms c_sq) to row i of x (fp32 [n, D]) under
+    focal_knn_search's distance, ordered by (d2, k) (focal_kmeans_assign: one launch, no host read).  labels (int32 [R, n]) is written in
+    place when given; min_d2 (fp32 [R, n], or want_min_d2) receives the chosen distance; changed (int32 [R]) += the rows whose label
+    differs from the one `labels` held on entry.  Returns labels, or (labels, min_d2) when min_d2 was asked for."""
+    n, D, K, R = _kmeans_args("kmeans_assign", x, c, c_sq, K)
+    _need_cuda(labels, min_d2, changed)
+    if labels is None:
+        labels = torch.full((R, n), -1, dtype=torch.int32, device=x.device)
+    if min_d2 is None and want_min_d2:
+        min_d2 = torch.empty(R, n, dtype=torch.float32, device=x.device)
+    if labels.dtype != torch.int32 or labels.numel() != R * n or not labels.is_contiguous():
+        raise _lib.FocalHipError(f"kmeans_assign: labels must be contiguous int32 [{R}, {n}]")
+    if min_d2 is not None and (min_d2.dtype != torch.float32 or min_d2.numel() != R * n or not min_d2.is_contiguous()):
+        raise _lib.FocalHipError(f"kmeans_assign: min_d2 must be contiguous fp32 [{R}, {n}]")
+    if changed is not None and (changed.dtype != torch.int32 or changed.numel() != R or not changed.is_contiguous()):
+        raise _lib.FocalHipError(f"kmeans_assign: changed must be contiguous int32 [{R}]")
+    d = _lib.KMeansDesc(n, D, K, R, 1)
+    check(_lib.load().focal_kmeans_assign(C.byref(d), _p(x), _p(c), _p(c_sq), _p(labels), _p(min_d2), _p(changed), _stream()))
+    return labels if min_d2 is None else (labels, min_d2)
+
+
+def kmeans_workspace(n, D, K, R, slices, device):
+    """The workspace of kmeans_update for these sizes (uint8; reusable across calls)."""
+    kmeans_check_limits(D, K, R)
+    d = _lib.KMeansDesc(n, D, K, R, slices)
+    return torch.empty(_lib.load().focal_kmeans_update_workspace(C.byref(d)), dtype=torch.uint8, device=device)
+
+
+def kmeans_update(x, labels, c, c_sq, K, min_d2=None, counts=None, inertia=None, slices=None, workspace=None):
+    """c[r * K + k] <- the mean of the rows of x labelled k in restart r, c_sq its squared norm, both IN PLACE; an empty cluster keeps
+    its centroid, bits unchanged (focal_kmeans_update: two launches, no floating-point atomics, no host read).  Returns (counts int32
+    [R, K], inertia fp32 [R] = the sums of min_d2's rows, or None without min_d2).  The results are bit-identical for equal arguments;
+    they depend on `slices` (None: kmeans_default_slices), which fixes the order of the sums.  workspace: kmeans_workspace(...), so
+    that repeated calls allocate nothing."""
+    n, D, K, R = _kmeans_args("kmeans_update", x, c, c_sq, K)
+    _need_cuda(labels, min_d2, counts, inertia, workspace)
+    if labels.dtype != torch.int32 or labels.numel() != R * n or not labels.is_contiguous():
+        raise _lib.FocalHipError(f"kmeans_update: labels must be contiguous int32 [{R}, {n}]")
+    if min_d2 is not None and (min_d2.dtype != torch.float32 or min_d2.numel() != R * n or not min_d2.is_contiguous()):
+        raise _lib.FocalHipError(f"kmeans_update: min_d2 must be contiguous fp32 [{R}, {n}]")
+    slices = kmeans_default_slices(n, D, x.device) if slices is None else int(slices)
+    if not 1 <= slices <= 65535:
+        raise _lib.FocalHipError(f"kmeans_update: need 1 <= slices <= 65535 (got {slices})")
+    if counts is None:
+        counts = torch.empty(R, K, dtype=torch.int32, device=x.device)
+    if inertia is None and min_d2 is not None:
+        inertia = torch.empty(R, dtype=torch.float32, device=x.device)
+    if counts.dtype != torch.int32 or counts.numel() != R * K or not counts.is_contiguous():
+        raise _lib.FocalHipError(f"kmeans_update: counts must be contiguous int32 [{R}, {K}]")
+    if inertia is not None and (min_d2 is None or inertia.dtype != torch.float32 or inertia.numel() != R or not inertia.is_contiguous()):
+        raise _lib.FocalHipError(f"kmeans_update: inertia must be contiguous fp32 [{R}] and needs min_d2")
+    if workspace is None:
+        workspace = kmeans_workspace(n, D, K, R, slices, x.device)
+    d = _lib.KMeansDesc(n, D, K, R, slices)
+    check(_lib.load().focal_kmeans_update(C.byref(d), _p(x), _p(labels), _p(min_d2), _p(c), _p(c_sq), _p(counts), _p(inertia), _p(workspace),
+                                          workspace.numel() * workspace.element_size(), _stream()))
+    return counts, inertia
+
+
 def mean_time(x, B, T, D):
     y = torch.empty(B, D, dtype=torch.float32, device=x.device)
     check(_lib.load().focal_mean_time(B, T, D, _p(x), _p(y), _stream()))

@@ -25,6 +25,11 @@ def parse_base_args(option="train"):
     p.add_argument("-config", type=str, default=None, help="[build extension] dataset YAML to use instead of ./data/{dataset}.yaml.")
     p.add_argument("-sync_bn", action="store_true", help="[build extension] DeepSense under torchrun: cross-rank BatchNorm statistics.")
     p.add_argument("-knn_k", type=int, default=5, help="[build extension] eval_knn.py: neighbours of the KNN estimator (the reference fits sklearn's default, 5).")
+    p.add_argument("-n_clusters", type=int, default=None, help="[build extension] eval_cluster.py: clusters of the K-means estimator (default: the task's num_classes; 1 .. 64).")
+    p.add_argument("-cluster_n_init", type=int, default=10, help="[build extension] eval_cluster.py: K-means restarts, the lowest inertia kept.")
+    p.add_argument("-cluster_max_iter", type=int, default=100, help="[build extension] eval_cluster.py: Lloyd iterations per restart at the most.")
+    p.add_argument("-cluster_init", type=str, default="k-means++", choices=["k-means++", "random"], help="[build extension] eval_cluster.py: seeding of the restarts.")
+    p.add_argument("-cluster_seed", type=int, default=0, help="[build extension] eval_cluster.py: seed of the seeding's draws.")
     args = p.parse_args()
     args.option = option
     return args

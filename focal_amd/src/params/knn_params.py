@@ -6,9 +6,9 @@ from params.base_params import parse_base_args
 from params.params_util import set_auto_params
 
 
-def refuse_other_frameworks(args):
+def refuse_other_frameworks(args, tool="eval_knn.py", score="the KNN accuracy of its features"):
     if args.learn_framework != "FOCAL":
-        raise ValueError(f"eval_knn.py scores the backbone of a FOCAL pretraining run by the KNN accuracy of its features; "
+        raise ValueError(f"{tool} scores the backbone of a FOCAL pretraining run by {score}; "
                          f"-learn_framework={args.learn_framework} trains a classifier: evaluate that with "
                          f"`python test.py -model={args.model} -dataset={args.dataset} -learn_framework={args.learn_framework}`")
 
@@ -28,7 +28,7 @@ def resolve_backbone_weight(args):
     return os.path.join(folder, f"{args.dataset}_{args.model}_pretrain_best.pt")
 
 
-def refuse_classifier_checkpoint(args, path):
+def refuse_classifier_checkpoint(args, path, tool="eval_knn.py"):
     """A finetuned or supervised classifier's checkpoint is scored by test.py, on its own class layer.  It is told by the name its training
     loop gave it (`*_finetune_{best,latest}.pt`, `{dataset}_{model}_{task}_{best,latest}.pt`) -- not by its tensors: a backbone's state dict
     holds `class_layer.*` at every stage, pretraining's checkpoints included, where they are the untouched initialisation."""
@@ -38,7 +38,7 @@ def refuse_classifier_checkpoint(args, path):
         stage = " -learn_framework=FOCAL -stage=finetune" if "_finetune_" in name else " -learn_framework=no"
         raise ValueError(f"{path} is a classifier checkpoint (the name finetuning / supervised training gives one): its class layer is what "
                          f"is scored, by `python test.py -model={args.model} -dataset={args.dataset}{stage} -model_weight={path}`; "
-                         f"eval_knn.py scores what `{pretraining_command(args)}` writes")
+                         f"{tool} scores what `{pretraining_command(args)}` writes")
 
 
 def parse_knn_params():

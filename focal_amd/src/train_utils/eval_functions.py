@@ -48,6 +48,45 @@ def metrics_from_confusion(args, conf):
     return mean_acc, mean_f1, conf[np.ix_(seen, seen)]
 
 
+def clustering_scores(conf, n_classes, n_clusters):
+    """(adjusted Rand index, normalised mutual information) of a clustering against the class labels, from the integer contingency
+    matrix alone: conf[label, cluster] counts, of which the leading [n_classes, n_clusters] block is read (ops.EvalState's matrix is
+    square, max(n_classes, n_clusters) wide).  float64 on the host; empty rows and columns are allowed.  sklearn's conventions
+    (adjusted_rand_score; normalized_mutual_info_score with its default arithmetic-mean normalisation): ARI from the pair counts, 1.0
+    when no pair is split either way; NMI 1.0 when one class meets one cluster (or there is no row), 0.0 when the mutual information
+    is 0."""
+    m = np.asarray(conf, dtype=np.int64)[:int(n_classes), :int(n_clusters)]
+    n = int(m.sum())
+    n_c, n_k = m.sum(axis=1), m.sum(axis=0)
+    # pairs: together in both (tp), in the clustering only (fp), in the classes only (fn), in neither (tn) -- exact integers
+    sum_sq = int((m.astype(object) ** 2).sum()) if m.size else 0
+    tp = sum_sq - n
+    fp = int((n_k.astype(object) ** 2).sum()) - sum_sq
+    fn = int((n_c.astype(object) ** 2).sum()) - sum_sq
+    tn = n * n - fp - fn - sum_sq
+    if fn == 0 and fp == 0:
+        ari = 1.0
+    else:
+        tp, fp, fn, tn = float(tp), float(fp), float(fn), float(tn)
+        ari = 2.0 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+    pi, pj = n_c[n_c > 0].astype(np.float64), n_k[n_k > 0].astype(np.float64)
+    if pi.size == pj.size == 1 or pi.size == pj.size == 0:
+        return ari, 1.0
+    nzx, nzy = np.nonzero(m)
+    nz = m[nzx, nzy].astype(np.float64)
+    outer = n_c[nzx].astype(np.int64) * n_k[nzy].astype(np.int64)
+    log_outer = -np.log(outer.astype(np.float64)) + np.log(pi.sum()) + np.log(pj.sum())
+    terms = (nz / n) * (np.log(nz) - np.log(float(n))) + (nz / n) * log_outer
+    terms = np.where(np.abs(terms) < np.finfo(terms.dtype).eps, 0.0, terms)
+    mi = float(np.clip(terms.sum(), 0.0, None))
+    if mi == 0.0:
+        return ari, 0.0
+
+    def entropy(p):
+        return 0.0 if p.size == 1 else float(-np.sum((p / p.sum()) * (np.log(p) - np.log(p.sum()))))
+    return ari, float(mi / (0.5 * (entropy(pi) + entropy(pj))))
+
+
 def eval_supervised_model(args, classifier, augmenter, dataloader, loss_func):
     """Loss and task metrics of a classifier (reference :29-62).  Loss and confusion matrix stay on the device (ops.EvalState: one
     launch per batch, whose batch loss is `CrossEntropyLoss`'s bit for bit); the host reads them once, after the loop.

@@ -694,6 +694,29 @@ int focal_knn_search(const focal_knn_desc* d, const float* q, const float* t, co
                      void* stream);
 int focal_knn_vote(const focal_knn_desc* d, const float* part_d2, const int* part_idx, const long* t_labels, const long* q_labels,
                    long* preds, int* nbr_idx, float* nbr_d2, int* conf, void* stream);
+/* K-means on the same features (train_utils/kmeans.py: GpuKMeans, src/eval_cluster.py): R restarts of K centroids are ONE matrix c fp32
+ * [R*K, D], restart r in rows r*K .. r*K + K - 1, with c_sq fp32 [R*K] their squared norms; x is fp32 [n, D].  One Lloyd iteration of all
+ * restarts is focal_kmeans_assign + focal_kmeans_update: three launches, no allocation, no host read (capturable), x read twice while
+ * R * K <= 160 (beyond that the update reads it once per group of floor(160 / K) restarts), and no floating-point atomic: the same
+ * arguments give the same bits.
+ * focal_kmeans_assign: labels[r*n + i] (int [R, n], read AND written) <- the k that minimises d2(x_i, c[r*K + k]), ordered by (d2, k); d2
+ * is the very function of the two rows that focal_knn_search computes (so for R = 1 the labels are its nearest neighbour over c, bit for
+ * bit); a NaN distance orders behind every number and a row whose distances are all NaN gets 0.  The [n, R*K] distances exist in LDS
+ * tiles only.  min_d2 ([R, n] or NULL) receives d2 of the chosen centroid; changed (int [R] or NULL) += the rows of restart r whose
+ * label differs from the value labels held on entry (integer atomics; the caller zeroes it).  `slices` is not read.
+ * focal_kmeans_update: c[r*K + k] <- the mean of the rows labelled k in restart r (a label outside [0, K) joins no cluster) and c_sq its
+ * squared norm, both in place; an EMPTY cluster keeps its centroid and its norm, bits unchanged (sklearn relocates it instead).
+ * counts (int [R, K]) <- the cluster sizes; inertia ([R] or NULL, needs min_d2 [R, n]) <- the sum of min_d2 over the rows.  The rows are
+ * cut into `slices` contiguous slices whose partial sums are added in slice order: the results depend on `slices`, and on nothing else.
+ * ws: focal_kmeans_update_workspace(d) bytes (0 for a descriptor outside the limits), written before it is read.
+ * Limits (FOCAL_EINVAL before any launch): D >= 4, D % 4 == 0, 1 <= K <= 64, R >= 1, R * K <= 1024, n >= 1, 1 <= slices <= 65535, x and
+ * c 16-byte aligned. */
+typedef struct { int n, D, K, R, slices; } focal_kmeans_desc;
+int focal_kmeans_assign(const focal_kmeans_desc* d, const float* x, const float* c, const float* c_sq, int* labels, float* min_d2,
+                        int* changed, void* stream);
+size_t focal_kmeans_update_workspace(const focal_kmeans_desc* d);
+int focal_kmeans_update(const focal_kmeans_desc* d, const float* x, const int* labels, const float* min_d2, float* c, float* c_sq,
+                        int* counts, float* inertia, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ location fusion (SW_Transformer)
  * Multi-location datasets: per modality, the L location features of a sample are a sequence of L tokens that runs through
