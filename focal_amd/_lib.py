@@ -162,6 +162,14 @@ class KMeansDesc(C.Structure):
 KMEANS_MAX_K, KMEANS_MAX_CENTROIDS = 64, 1024
 
 
+class ProbeDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n", "D", "C", "R", "slices")]
+
+
+# focal_probe_forward / focal_probe_grad: the limits on the classes per problem and on all problems' weight rows (include/focal_hip.h)
+PROBE_MAX_C, PROBE_MAX_ROWS = 64, 1024
+
+
 class AdamWDesc(C.Structure):
     _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("l2_decay", C.c_int)]
 
@@ -253,6 +261,9 @@ PROTOTYPES = {
     "focal_kmeans_assign": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P]),
     "focal_kmeans_update_workspace": (C.c_size_t, [C.POINTER(KMeansDesc)]),
     "focal_kmeans_update": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P, P, C.c_size_t, P]),
+    "focal_probe_forward": (C.c_int, [C.POINTER(ProbeDesc), P, P, P, P, P, P, P, P]),
+    "focal_probe_grad_workspace": (C.c_size_t, [C.POINTER(ProbeDesc)]),
+    "focal_probe_grad": (C.c_int, [C.POINTER(ProbeDesc), P, P, P, P, P, P, P, P, P, C.c_size_t, P]),
     "focal_small_linear_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P]),
     "focal_small_linear_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "focal_loss_head_workspace": (C.c_size_t, [C.POINTER(LossDesc)]),

@@ -1491,6 +1491,128 @@ def kmeans_update(x, labels, c, c_sq, K, min_d2=None, counts=None, inertia=None,
     return counts, inertia
 
 
+def probe_check_limits(D, C_, R):
+    """The limits of focal_probe_forward / focal_probe_grad on the feature width, the classes per problem and the problems, refused here
+    with the limit named (the library refuses them too, before any launch)."""
+    if D < 4 or D % 4:
+        raise _lib.FocalHipError(f"probe: need a feature width D >= 4 with D % 4 == 0 (got D={D})")
+    if not 2 <= C_ <= _lib.PROBE_MAX_C:
+        raise _lib.FocalHipError(f"probe: need 2 <= C <= {_lib.PROBE_MAX_C} (got C={C_})")
+    if R < 1 or R * C_ > _lib.PROBE_MAX_ROWS:
+        raise _lib.FocalHipError(f"probe: need R >= 1 and R * C <= {_lib.PROBE_MAX_ROWS} (got R={R} C={C_})")
+
+
+def probe_default_slices(n, D, device):
+    """Row slices of focal_probe_grad: kmeans_default_slices' rule (about two workgroups per CU over the 64-column chunks of D), never
+    more than there are 64-row blocks."""
+    return kmeans_default_slices(n, D, device)
+
+
+def _probe_args(who, x, w, b, num_classes):
+    _need_cuda(x, w, b)
+    if x.dtype != torch.float32 or w.dtype != torch.float32 or b.dtype != torch.float32 or x.dim() != 2 or w.dim() != 2:
+        raise _lib.FocalHipError(f"{who}: x, w and b are fp32, x and w matrices")
+    if not (x.is_contiguous() and w.is_contiguous() and b.is_contiguous()):
+        raise _lib.FocalHipError(f"{who}: x, w and b must be contiguous")
+    n, D = x.shape
+    Cn = int(num_classes)
+    if Cn < 1 or w.shape[0] % Cn or w.shape[1] != D or b.numel() != w.shape[0]:
+        raise _lib.FocalHipError(f"{who}: x {tuple(x.shape)} against w {tuple(w.shape)}, {b.numel()} biases and C={Cn} "
+                                 f"(need 2 <= C <= {_lib.PROBE_MAX_C} and w [R * C, D])")
+    R = w.shape[0] // Cn
+    if n < 1:
+        raise _lib.FocalHipError(f"{who}: need n >= 1 (got n={n})")
+    probe_check_limits(D, Cn, R)
+    return n, D, Cn, R
+
+
+def probe_forward(x, w, b, num_classes, y=None, ce=None, g=None, preds=None, want_ce=False, want_g=False, want_preds=False,
+                  check_labels=True):
+    """The softmax pass of R problems (w fp32 [R * C, D], b fp32 [R * C]) over x (fp32 [n, D]) with labels y (int32 [n])
+    (focal_probe_forward: one launch).  Returns (ce fp32 [R, n], g fp32 [n, R * C] = softmax - onehot, preds int32 [R, n]), each None
+    unless given or asked for with want_*; a predict-only call needs no y.  check_labels refuses a label outside [0, C) before the
+    launch -- the pass's one host read: a caller that has checked its labels once (or captures the call) passes False."""
+    n, D, Cn, R = _probe_args("probe_forward", x, w, b, num_classes)
+    _need_cuda(y, ce, g, preds)
+    if ce is None and want_ce:
+        ce = torch.empty(R, n, dtype=torch.float32, device=x.device)
+    if g is None and want_g:
+        g = torch.empty(n, R * Cn, dtype=torch.float32, device=x.device)
+    if preds is None and want_preds:
+        preds = torch.empty(R, n, dtype=torch.int32, device=x.device)
+    if ce is None and g is None and preds is None:
+        raise _lib.FocalHipError("probe_forward: no output asked for (ce, g or preds)")
+    if ce is not None or g is not None:
+        if y is None or y.dtype != torch.int32 or y.numel() != n or not y.is_contiguous():
+            raise _lib.FocalHipError(f"probe_forward: ce and g need the labels y, contiguous int32 [{n}]")
+        if check_labels:
+            low, high = (int(v) for v in torch.stack([y.min(), y.max()]).cpu())
+            if low < 0 or high >= Cn:
+                raise _lib.FocalHipError(f"probe_forward: labels must lie in [0, {Cn}) (got {low} .. {high})")
+    else:
+        y = None
+    if ce is not None and (ce.dtype != torch.float32 or ce.numel() != R * n or not ce.is_contiguous()):
+        raise _lib.FocalHipError(f"probe_forward: ce must be contiguous fp32 [{R}, {n}]")
+    if g is not None and (g.dtype != torch.float32 or g.numel() != n * R * Cn or not g.is_contiguous()):
+        raise _lib.FocalHipError(f"probe_forward: g must be contiguous fp32 [{n}, {R * Cn}]")
+    if preds is not None and (preds.dtype != torch.int32 or preds.numel() != R * n or not preds.is_contiguous()):
+        raise _lib.FocalHipError(f"probe_forward: preds must be contiguous int32 [{R}, {n}]")
+    d = _lib.ProbeDesc(n, D, Cn, R, 1)
+    check(_lib.load().focal_probe_forward(C.byref(d), _p(x), _p(w), _p(b), _p(y), _p(ce), _p(g), _p(preds), _stream()))
+    return ce, g, preds
+
+
+def probe_workspace(n, D, num_classes, R, slices, device):
+    """The workspace of probe_grad for these sizes (uint8; reusable across calls)."""
+    probe_check_limits(D, num_classes, R)
+    d = _lib.ProbeDesc(n, D, num_classes, R, slices)
+    return torch.empty(_lib.load().focal_probe_grad_workspace(C.byref(d)), dtype=torch.uint8, device=device)
+
+
+def probe_grad(x, g, ce, w, lam, num_classes, gw=None, gb=None, f=None, slices=None, workspace=None):
+    """gw [R * C, D] = g^T x / n + lam_r W_r, gb [R * C] = the column means of g, f fp64 [R] = mean(ce_r) + lam_r / 2 |W_r|^2, from
+    probe_forward's g (fp32 [n, R * C]) and ce (fp32 [R, n]) (focal_probe_grad: two launches, no floating-point atomics, no host read).
+    lam: fp32 [R].  Returns (f, gw, gb), written in place when given.  The results are bit-identical for equal arguments; gw and gb
+    depend on `slices` (None: probe_default_slices), which fixes the order of the sums.  workspace: probe_workspace(...), so that
+    repeated calls allocate nothing."""
+    _need_cuda(x, g, ce, w, lam, gw, gb, f, workspace)
+    if any(t.dtype != torch.float32 for t in (x, g, ce, w, lam)) or x.dim() != 2 or w.dim() != 2:
+        raise _lib.FocalHipError("probe_grad: x, g, ce, w and lam are fp32, x and w matrices")
+    if not all(t.is_contiguous() for t in (x, g, ce, w, lam)):
+        raise _lib.FocalHipError("probe_grad: x, g, ce, w and lam must be contiguous")
+    n, D = x.shape
+    Cn = int(num_classes)
+    if Cn < 1 or w.shape[0] % Cn or w.shape[1] != D:
+        raise _lib.FocalHipError(f"probe_grad: x {tuple(x.shape)} against w {tuple(w.shape)} and C={Cn} (need w [R * C, D])")
+    R = w.shape[0] // Cn
+    if n < 1:
+        raise _lib.FocalHipError(f"probe_grad: need n >= 1 (got n={n})")
+    probe_check_limits(D, Cn, R)
+    if g.numel() != n * R * Cn or ce.numel() != R * n or lam.numel() != R:
+        raise _lib.FocalHipError(f"probe_grad: need g [{n}, {R * Cn}], ce [{R}, {n}] and lam [{R}]")
+    slices = probe_default_slices(n, D, x.device) if slices is None else int(slices)
+    if not 1 <= slices <= 65535:
+        raise _lib.FocalHipError(f"probe_grad: need 1 <= slices <= 65535 (got {slices})")
+    if gw is None:
+        gw = torch.empty(R * Cn, D, dtype=torch.float32, device=x.device)
+    if gb is None:
+        gb = torch.empty(R * Cn, dtype=torch.float32, device=x.device)
+    if f is None:
+        f = torch.empty(R, dtype=torch.float64, device=x.device)
+    if gw.dtype != torch.float32 or gw.numel() != R * Cn * D or not gw.is_contiguous():
+        raise _lib.FocalHipError(f"probe_grad: gw must be contiguous fp32 [{R * Cn}, {D}]")
+    if gb.dtype != torch.float32 or gb.numel() != R * Cn or not gb.is_contiguous():
+        raise _lib.FocalHipError(f"probe_grad: gb must be contiguous fp32 [{R * Cn}]")
+    if f.dtype != torch.float64 or f.numel() != R or not f.is_contiguous():
+        raise _lib.FocalHipError(f"probe_grad: f must be contiguous fp64 [{R}]")
+    if workspace is None:
+        workspace = probe_workspace(n, D, Cn, R, slices, x.device)
+    d = _lib.ProbeDesc(n, D, Cn, R, slices)
+    check(_lib.load().focal_probe_grad(C.byref(d), _p(x), _p(g), _p(ce), _p(w), _p(lam), _p(gw), _p(gb), _p(f), _p(workspace),
+                                       workspace.numel() * workspace.element_size(), _stream()))
+    return f, gw, gb
+
+
 def mean_time(x, B, T, D):
     y = torch.empty(B, D, dtype=torch.float32, device=x.device)
     check(_lib.load().focal_mean_time(B, T, D, _p(x), _p(y), _stream()))

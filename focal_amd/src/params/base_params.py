@@ -30,6 +30,9 @@ def parse_base_args(option="train"):
     p.add_argument("-cluster_max_iter", type=int, default=100, help="[build extension] eval_cluster.py: Lloyd iterations per restart at the most.")
     p.add_argument("-cluster_init", type=str, default="k-means++", choices=["k-means++", "random"], help="[build extension] eval_cluster.py: seeding of the restarts.")
     p.add_argument("-cluster_seed", type=int, default=0, help="[build extension] eval_cluster.py: seed of the seeding's draws.")
+    p.add_argument("-probe_l2", type=str, default="1e-4,1e-3,1e-2,1e-1", help="[build extension] eval_linear.py: comma list of L2 strengths (at most 16), all fitted in one pass; the one with the highest validation accuracy is reported on the test split.")
+    p.add_argument("-probe_max_iter", type=int, default=200, help="[build extension] eval_linear.py: L-BFGS steps per strength at the most.")
+    p.add_argument("-probe_tol", type=float, default=1e-5, help="[build extension] eval_linear.py: a strength has converged when its largest gradient entry is at most this.")
     args = p.parse_args()
     args.option = option
     return args

@@ -717,6 +717,30 @@ int focal_kmeans_assign(const focal_kmeans_desc* d, const float* x, const float*
 size_t focal_kmeans_update_workspace(const focal_kmeans_desc* d);
 int focal_kmeans_update(const focal_kmeans_desc* d, const float* x, const int* labels, const float* min_d2, float* c, float* c_sq,
                         int* counts, float* inertia, void* ws, size_t ws_bytes, void* stream);
+/* Linear probe on the same features (train_utils/linear_probe.py: GpuLinearProbe, src/eval_linear.py): the objective and gradient of
+ * softmax regression for R regularisation strengths at once.  Problem r holds W_r [C, D], b_r [C] and lambda_r; all problems are ONE
+ * matrix w fp32 [R*C, D] with b fp32 [R*C] and lam fp32 [R]; x is fp32 [n, D], y int [n] the class of each row.
+ *   F_r = (1/n) sum_i CE(softmax(W_r x_i + b_r), y_i) + (lambda_r / 2) |W_r|^2          (the bias is not penalised)
+ * One evaluation is focal_probe_forward + focal_probe_grad: three launches, no allocation, no host read (capturable), x read twice
+ * while R * C <= 64 (beyond that the gradient pass reads it once per 64-row chunk of R*C), and no floating-point atomic: the same
+ * arguments give the same bits, and a problem's outputs do not depend on which other problems share the launch.
+ * focal_probe_forward: z = x w^T + b by the exact-fp32 product of focal_knn_search, held in LDS tiles only; per row and problem the
+ * log-sum-exp with the maximum subtracted (expf / logf, not the fast intrinsics).  Writes whichever of these is not NULL:
+ * ce [R, n] = lse - z_y; g [n, R*C] = softmax - onehot; preds int [R, n] = the arg-max class, ties to the smallest class, a NaN logit
+ * never beats a number (all NaN: 0).  ce and g need y; a predict-only call passes NULL for y, ce and g.  y is NOT range-checked on the
+ * device (the caller refuses labels outside [0, C) before the launch); such a label selects no logit and no one-hot.  `slices` is
+ * not read.
+ * focal_probe_grad: gw [R*C, D] = (1/n) g^T x + lambda_r W_r, gb [R*C] = (1/n) sum_i g, f double [R] = F_r from ce and w.  The rows
+ * are cut into `slices` contiguous slices whose partial products are added in slice order: gw and gb depend on `slices`, and on
+ * nothing else.  ws: focal_probe_grad_workspace(d) bytes (0 for a descriptor outside the limits), written before it is read.
+ * Limits (FOCAL_EINVAL before any launch): D >= 4, D % 4 == 0, 2 <= C <= 64, R >= 1, R * C <= 1024, n >= 1, 1 <= slices <= 65535, x
+ * and w 16-byte aligned. */
+typedef struct { int n, D, C, R, slices; } focal_probe_desc;
+int focal_probe_forward(const focal_probe_desc* d, const float* x, const float* w, const float* b, const int* y, float* ce, float* g,
+                        int* preds, void* stream);
+size_t focal_probe_grad_workspace(const focal_probe_desc* d);
+int focal_probe_grad(const focal_probe_desc* d, const float* x, const float* g, const float* ce, const float* w, const float* lam,
+                     float* gw, float* gb, double* f, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ location fusion (SW_Transformer)
  * Multi-location datasets: per modality, the L location features of a sample are a sequence of L tokens that runs through
