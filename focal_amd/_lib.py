@@ -170,6 +170,14 @@ class ProbeDesc(C.Structure):
 PROBE_MAX_C, PROBE_MAX_ROWS = 64, 1024
 
 
+class TsneDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n", "D", "slices")]
+
+
+# focal_tsne_*: the largest row count (a row of distances in LDS), rows per gradient workgroup, columns per LDS chunk (include/focal_hip.h)
+TSNE_MAX_N, TSNE_ROW_TILE, TSNE_COL_CHUNK = 32768, 32, 2048
+
+
 class AdamWDesc(C.Structure):
     _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("l2_decay", C.c_int)]
 
@@ -264,6 +272,13 @@ PROTOTYPES = {
     "focal_probe_forward": (C.c_int, [C.POINTER(ProbeDesc), P, P, P, P, P, P, P, P]),
     "focal_probe_grad_workspace": (C.c_size_t, [C.POINTER(ProbeDesc)]),
     "focal_probe_grad": (C.c_int, [C.POINTER(ProbeDesc), P, P, P, P, P, P, P, P, P, C.c_size_t, P]),
+    "focal_tsne_dist": (C.c_int, [C.POINTER(TsneDesc), P, P, P, P]),
+    "focal_tsne_perplexity": (C.c_int, [C.POINTER(TsneDesc), C.c_float, P, P, P]),
+    "focal_tsne_symmetrize_workspace": (C.c_size_t, [C.POINTER(TsneDesc)]),
+    "focal_tsne_symmetrize": (C.c_int, [C.POINTER(TsneDesc), P, P, P, C.c_size_t, P]),
+    "focal_tsne_grad_workspace": (C.c_size_t, [C.POINTER(TsneDesc)]),
+    "focal_tsne_grad": (C.c_int, [C.POINTER(TsneDesc), P, P, C.c_int, P, C.c_size_t, P]),
+    "focal_tsne_step": (C.c_int, [C.POINTER(TsneDesc), P, C.c_size_t, P, P, P, P, C.c_float, C.c_float, C.c_float, C.c_int, P, C.c_int, P]),
     "focal_small_linear_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P]),
     "focal_small_linear_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "focal_loss_head_workspace": (C.c_size_t, [C.POINTER(LossDesc)]),

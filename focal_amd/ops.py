@@ -1613,6 +1613,118 @@ def probe_grad(x, g, ce, w, lam, num_classes, gw=None, gb=None, f=None, slices=N
     return f, gw, gb
 
 
+def tsne_check_limits(n, D, perplexity=None):
+    """The limits of the focal_tsne_* exports on the row count, the feature width and the perplexity, refused here with the limit named
+    (the library refuses them too, before any launch)."""
+    if D < 4 or D % 4:
+        raise _lib.FocalHipError(f"tsne: need a feature width D >= 4 with D % 4 == 0 (got D={D})")
+    if not 2 <= n <= _lib.TSNE_MAX_N:
+        raise _lib.FocalHipError(f"tsne: need 2 <= n <= {_lib.TSNE_MAX_N} (got n={n}): a row of the distance matrix is held in LDS")
+    if perplexity is not None and not 1 <= float(perplexity) < n:
+        raise _lib.FocalHipError(f"tsne: need 1 <= perplexity < n (got perplexity={perplexity} n={n})")
+
+
+def tsne_default_slices(n, device):
+    """Column slices of focal_tsne_grad: knn_default_slices' rule (about two workgroups per CU) over the gradient's 32-row tiles, never
+    more than there are 2048-column chunks."""
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    row_tiles = -(-n // _lib.TSNE_ROW_TILE)
+    return max(1, min(-(-n // _lib.TSNE_COL_CHUNK), round(2 * cus / row_tiles)))
+
+
+def _tsne_x(who, x):
+    _need_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise _lib.FocalHipError(f"{who}: x is an fp32 matrix [n, D]")
+    return x.shape
+
+
+def tsne_dist(x, want_norms=False):
+    """d2 fp32 [n, n] of the rows of x (fp32 [n, D]) under focal_knn_search's distance, diagonal +0 (focal_tsne_dist: two launches).
+    want_norms: also x_sq [n], the squared norms the kernel used -- handed to knn_search_vote as t_sq, its nbr_d2 are these bits."""
+    n, D = _tsne_x("tsne_dist", x)
+    tsne_check_limits(n, D)
+    d2 = torch.empty(n, n, dtype=torch.float32, device=x.device)
+    x_sq = torch.empty(n, dtype=torch.float32, device=x.device)
+    d = _lib.TsneDesc(n, D, 1)
+    check(_lib.load().focal_tsne_dist(C.byref(d), _p(x), _p(x_sq), _p(d2), _stream()))
+    return (d2, x_sq) if want_norms else d2
+
+
+def tsne_affinities(x, perplexity, want_conditional=False):
+    """The joint probabilities of exact t-SNE for the rows of x (fp32 [n, D]): distances, 64 bisection steps per row on beta, and the
+    symmetrisation, in ONE [n, n] buffer (focal_tsne_dist + focal_tsne_perplexity + focal_tsne_symmetrize; no host read).  Returns
+    (P fp32 [n, n], bitwise symmetric with a zero diagonal; beta fp32 [n]; p_log_p fp64 [1] = sum P log P), and with want_conditional
+    a copy of the conditional matrix p_j|i as a fourth value."""
+    n, D = _tsne_x("tsne_affinities", x)
+    tsne_check_limits(n, D, perplexity)
+    lib = _lib.load()
+    d = _lib.TsneDesc(n, D, 1)
+    P = torch.empty(n, n, dtype=torch.float32, device=x.device)
+    beta = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(lib.focal_tsne_dist(C.byref(d), _p(x), _p(beta), _p(P), _stream()))  # (beta holds the norms until the bisection writes it)
+    check(lib.focal_tsne_perplexity(C.byref(d), float(perplexity), _p(P), _p(beta), _stream()))
+    cond = P.clone() if want_conditional else None
+    ws = torch.empty(lib.focal_tsne_symmetrize_workspace(C.byref(d)), dtype=torch.uint8, device=x.device)
+    p_log_p = torch.empty(1, dtype=torch.float64, device=x.device)
+    check(lib.focal_tsne_symmetrize(C.byref(d), _p(P), _p(p_log_p), _p(ws), ws.numel(), _stream()))
+    return (P, beta, p_log_p, cond) if want_conditional else (P, beta, p_log_p)
+
+
+def tsne_workspace(n, slices, device):
+    """The workspace of tsne_grad_step for these sizes (uint8; reusable across calls)."""
+    d = _lib.TsneDesc(n, 4, slices)
+    return torch.empty(_lib.load().focal_tsne_grad_workspace(C.byref(d)), dtype=torch.uint8, device=device)
+
+
+def tsne_record(entries, device):
+    """A zeroed device record for tsne_grad_step with room for `entries` KL entries: fp64 [2 + 3 * entries] = {iterations, entries
+    written, (iteration, KL, gradient norm) ...}."""
+    return torch.zeros(2 + 3 * int(entries), dtype=torch.float64, device=device)
+
+
+def tsne_read_record(record):
+    """The record's one host read: (iterations, float64 tensor [entries, 3] of (iteration, KL, gradient norm))."""
+    host = record.cpu()
+    k = min(int(host[1].item()), (host.numel() - 2) // 3)
+    return int(host[0].item()), host[2:2 + 3 * k].view(k, 3)
+
+
+def tsne_grad_step(y, P, p_log_p, upd, gains, lr, momentum, exaggeration, record=None, want_kl=False, slices=None, workspace=None):
+    """One descent iteration of exact t-SNE, IN PLACE on y, upd and gains (each fp32 [n, 2]): the gradient of KL(e P || Q) from one read
+    of P (fp32 [n, n]) and sklearn's gains / momentum update (focal_tsne_grad + focal_tsne_step: two launches, no floating-point
+    atomics, no host read).  record (tsne_record) counts the call; with want_kl the entry (iteration, KL, |g|_2) is appended to it, KL =
+    p_log_p - sum P log q + log Z being the divergence at exaggeration 1 only.  The results are bit-identical for equal arguments;
+    they depend on `slices` (None: tsne_default_slices), which fixes the order of the sums.  workspace: tsne_workspace(...), so that
+    repeated calls allocate nothing."""
+    _need_cuda(y, P, p_log_p, upd, gains, record, workspace)
+    n = y.shape[0]
+    if any(t.dtype != torch.float32 or tuple(t.shape) != (n, 2) for t in (y, upd, gains)):
+        raise _lib.FocalHipError(f"tsne_grad_step: y, upd and gains are fp32 [{n}, 2]")
+    if P.dtype != torch.float32 or tuple(P.shape) != (n, n):
+        raise _lib.FocalHipError(f"tsne_grad_step: P must be fp32 [{n}, {n}]")
+    tsne_check_limits(n, 4)
+    slices = tsne_default_slices(n, y.device) if slices is None else int(slices)
+    if not 1 <= slices <= 65535:
+        raise _lib.FocalHipError(f"tsne_grad_step: need 1 <= slices <= 65535 (got {slices})")
+    cap = 0
+    if record is not None:
+        if record.dtype != torch.float64 or record.dim() != 1 or record.numel() < 2 or (record.numel() - 2) % 3:
+            raise _lib.FocalHipError("tsne_grad_step: record must be fp64 [2 + 3 * entries] (tsne_record)")
+        cap = (record.numel() - 2) // 3
+    if want_kl and (cap < 1 or p_log_p is None or p_log_p.dtype != torch.float64 or p_log_p.numel() != 1):
+        raise _lib.FocalHipError("tsne_grad_step: want_kl needs p_log_p fp64 [1] and a record with room for an entry")
+    if workspace is None:
+        workspace = tsne_workspace(n, slices, y.device)
+    d = _lib.TsneDesc(n, 4, slices)
+    lib = _lib.load()
+    ws_bytes = workspace.numel() * workspace.element_size()
+    check(lib.focal_tsne_grad(C.byref(d), _p(y), _p(P), int(bool(want_kl)), _p(workspace), ws_bytes, _stream()))
+    check(lib.focal_tsne_step(C.byref(d), _p(workspace), ws_bytes, _p(p_log_p), _p(y), _p(upd), _p(gains), float(lr), float(momentum),
+                              float(exaggeration), int(bool(want_kl)), _p(record), cap, _stream()))
+    return y
+
+
 def mean_time(x, B, T, D):
     y = torch.empty(B, D, dtype=torch.float32, device=x.device)
     check(_lib.load().focal_mean_time(B, T, D, _p(x), _p(y), _stream()))

@@ -287,8 +287,11 @@ class SwinModEncoder:
         K = last["H"] * last["W"] * last["C"]
         pin = f"mod_in_layers.{self.loc}.{self.mod}"
         n_out = bb.config["loc_out_channels"]
-        splits = max(1, min(32, K // 512))
-        d_in = ops.linear_desc(f32 if tail_fp32(bb) else cc, B, n_out, K, f32, f32, splits=splits)
+        # The training step cuts K into up to 32 splits whose partial products meet in fp32 atomics: the order of those adds, and so the
+        # last bits of the features, differ from call to call.  An evaluation pass takes the one k-ordered sum instead, so that a saved
+        # checkpoint's features -- and every score or map made of them -- repeat bit for bit.
+        splits = max(1, min(32, K // 512)) if training else 1
+        d_in =ops.linear_desc(f32 if tail_fp32(bb) else cc, B, n_out, K, f32, f32, splits=splits)
         feat = torch.zeros(B, n_out, dtype=torch.float32, device=x.device)
         ops.linear_fwd(d_in, x, tail_weight(bb, ar, f"{pin}.weight"), ar.master(f"{pin}.bias"), None, feat)
         saved.update(x_final=x, d_in=d_in, pin=pin)

@@ -741,6 +741,37 @@ int focal_probe_forward(const focal_probe_desc* d, const float* x, const float* 
 size_t focal_probe_grad_workspace(const focal_probe_desc* d);
 int focal_probe_grad(const focal_probe_desc* d, const float* x, const float* g, const float* ce, const float* w, const float* lam,
                      float* gw, float* gb, double* f, void* ws, size_t ws_bytes, void* stream);
+/* Exact t-SNE of the same features (train_utils/tsne.py: GpuTSNE, src/eval_tsne.py): x fp32 [n, D] -> y fp32 [n, 2].  Three setup calls
+ * build the joint-probability matrix P fp32 [n, n] in ONE buffer, in place; one descent iteration is focal_tsne_grad + focal_tsne_step:
+ * two launches, P read once, no [n, n] temporary, no allocation, no host read (capturable), no floating-point atomic: the same arguments,
+ * `slices` included, give the same bits.  Every [n, n] offset is 64-bit.
+ * focal_tsne_dist: x_sq [n] <- the rows' squared norms by focal_knn_search's tree for |q|^2; d2 [n, n] <- (|x_i|^2 + |x_j|^2) - 2 x_i.x_j,
+ * the very function of the two rows that focal_knn_search computes when handed x_sq as t_sq; the diagonal is written as +0.
+ * focal_tsne_perplexity: per row i, beta_i by exactly 64 steps (beta = 1; doubled while no upper bound exists, bisected after; no early
+ * exit) on H(beta) = log sum p + beta sum (d2 - dmin) p / sum p against log(perplexity), p_j = exp(-(d2_ij - dmin_i) beta) over j != i with
+ * dmin_i the row's smallest off-diagonal distance; H > log(perplexity) raises the lower bound.  p (holding d2 on entry) <- the conditional
+ * row p_j|i, diagonal 0; beta [n] <- beta_i.  One workgroup per row with the row in LDS: n <= 32 768.
+ * focal_tsne_symmetrize: p <- (p_j|i + p_i|j) / 2n, bitwise symmetric, diagonal 0; p_log_p (one double) <- sum P log P, from per-tile
+ * double partials in ws (focal_tsne_symmetrize_workspace(d) bytes) added in tile order.
+ * focal_tsne_grad: with q_ij = 1 / (1 + |y_i - y_j|^2) over j != i, per row and column slice the partial sums of P q (y_i - y_j) (2),
+ * q^2 (y_i - y_j) (2), q, and with want_kl P log q, to ws laid out [slices][6][n] (focal_tsne_grad_workspace(d) bytes).  The columns are
+ * cut into `slices` contiguous slices of ceil(n / slices) columns rounded up to a multiple of 4.
+ * focal_tsne_step (one workgroup): Z = sum q in double, g_i = 4 (exaggeration attr_i - rep_i / Z) with the slices added in slice order,
+ * then sklearn's update: gains <- (upd g < 0 ? gains + 0.2 : gains 0.8) floored at 0.01, upd <- momentum upd - lr gains g, y += upd.
+ * record (double [2 + 3 cap] or NULL): record[0] += 1 per call (the iteration count); with want_kl the entry {iteration, KL = sum P log P -
+ * sum P log q + log Z, |g|_2} is appended at 2 + 3 record[1] while record[1] < cap, and record[1] += 1.  KL is the divergence only at
+ * exaggeration 1.  want_kl must be the value focal_tsne_grad was called with.
+ * Limits (FOCAL_EINVAL before any launch): D >= 4, D % 4 == 0, 2 <= n <= 32768, 1 <= perplexity < n, 1 <= slices <= 65535, x and p
+ * 16-byte aligned. */
+typedef struct { int n, D, slices; } focal_tsne_desc;
+int focal_tsne_dist(const focal_tsne_desc* d, const float* x, float* x_sq, float* d2, void* stream);
+int focal_tsne_perplexity(const focal_tsne_desc* d, float perplexity, float* p, float* beta, void* stream);
+size_t focal_tsne_symmetrize_workspace(const focal_tsne_desc* d);
+int focal_tsne_symmetrize(const focal_tsne_desc* d, float* p, double* p_log_p, void* ws, size_t ws_bytes, void* stream);
+size_t focal_tsne_grad_workspace(const focal_tsne_desc* d);
+int focal_tsne_grad(const focal_tsne_desc* d, const float* y, const float* p, int want_kl, void* ws, size_t ws_bytes, void* stream);
+int focal_tsne_step(const focal_tsne_desc* d, const void* ws, size_t ws_bytes, const double* p_log_p, float* y, float* upd, float* gains,
+                    float lr, float momentum, float exaggeration, int want_kl, double* record, int record_cap, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ location fusion (SW_Transformer)
  * Multi-location datasets: per modality, the L location features of a sample are a sequence of L tokens that runs through
