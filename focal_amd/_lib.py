@@ -154,6 +154,14 @@ class KnnDesc(C.Structure):
 KNN_QUERY_TILE, KNN_TRAIN_TILE, KNN_MAX_K, KNN_MAX_CLASSES = 128, 64, 16, 64
 
 
+class RankDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("nq", "nt", "D", "slices")]
+
+
+# focal_rank_positive: the largest `slices` (include/focal_hip.h)
+RANK_MAX_SLICES = 65535
+
+
 class KMeansDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n", "D", "K", "R", "slices")]
 
@@ -266,6 +274,8 @@ PROTOTYPES = {
     "focal_eval_accumulate": (C.c_int, [C.c_int, C.c_int, P, P, P, P, P, P, P]),
     "focal_knn_search": (C.c_int, [C.POINTER(KnnDesc), P, P, P, P, P, P]),
     "focal_knn_vote": (C.c_int, [C.POINTER(KnnDesc), P, P, P, P, P, P, P, P, P]),
+    "focal_rank_workspace": (C.c_size_t, [C.POINTER(RankDesc)]),
+    "focal_rank_positive": (C.c_int, [C.POINTER(RankDesc), P, P, P, P, P, P, P, P, C.c_size_t, P]),
     "focal_kmeans_assign": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P]),
     "focal_kmeans_update_workspace": (C.c_size_t, [C.POINTER(KMeansDesc)]),
     "focal_kmeans_update": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P, P, C.c_size_t, P]),

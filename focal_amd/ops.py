@@ -1396,6 +1396,51 @@ def knn_search_vote(q, t, t_sq, t_labels, k, n_classes, q_labels=None, conf=None
     return (preds, nbr_idx, nbr_d2) if want_neighbours else preds
 
 
+def rank_check_limits(D, nq, nt, slices):
+    """The limits of focal_rank_positive on the feature width, the row counts and the slices, refused here with the library's own text
+    (it refuses them too, before any launch)."""
+    if D < 4 or D % 4:
+        raise _lib.FocalHipError(f"rank_positive: need D >= 4 and D % 4 == 0 (got D={D})")
+    if nq < 1 or nt < 1:
+        raise _lib.FocalHipError(f"rank_positive: need nq >= 1 and nt >= 1 (got nq={nq} nt={nt})")
+    if not 1 <= slices <= _lib.RANK_MAX_SLICES:
+        raise _lib.FocalHipError(f"rank_positive: need 1 <= slices <= {_lib.RANK_MAX_SLICES} (got slices={slices})")
+
+
+def rank_positive(q, t, t_sq, pos, slices=None, want_d2=False):
+    """Where row pos[i] of t (fp32 [nt, D], squared norms t_sq [nt]) lands among all rows of t ranked for query q[i] (fp32 [nq, D]) under
+    focal_knn_search's distance and (d2, index) order (focal_rank_positive: two launches, no host read, no [nq, nt] tensor).  Returns
+    before (int32 [nq], the rows ordering before the positive: its rank is before + 1) and tied (int32 [nq], the other rows at exactly the
+    positive's distance); with want_d2 also pos_d2 (fp32 [nq]), the bits the search gives that pair.  A pos outside [0, nt) gives
+    -1 / -1 / NaN.  The results do not depend on `slices` (None: knn_default_slices)."""
+    _need_cuda(q, t, t_sq, pos)
+    if q.dtype != torch.float32 or t.dtype != torch.float32 or t_sq.dtype != torch.float32 or q.dim() != 2 or t.dim() != 2:
+        raise _lib.FocalHipError("rank_positive: q, t and t_sq are fp32, q and t matrices")
+    nq, D = q.shape
+    nt = t.shape[0]
+    if t.shape[1] != D or t_sq.numel() != nt or pos.dtype != torch.int32 or pos.numel() != nq:
+        raise _lib.FocalHipError(f"rank_positive: q {tuple(q.shape)} against t {tuple(t.shape)}, {t_sq.numel()} norms and "
+                                 f"{pos.numel()} {pos.dtype} positives (need int32 [nq])")
+    if not (q.is_contiguous() and t.is_contiguous() and t_sq.is_contiguous() and pos.is_contiguous()):
+        raise _lib.FocalHipError("rank_positive: q, t, t_sq and pos must be contiguous")
+    if nq >= 1 and nt >= 1 and D >= 4 and D % 4 == 0 and slices is None:
+        slices = knn_default_slices(nq, nt, q.device)
+    slices = 1 if slices is None else int(slices)
+    rank_check_limits(D, nq, nt, slices)
+    if q.data_ptr() % 16 or t.data_ptr() % 16:
+        raise _lib.FocalHipError("rank_positive: q and t must be 16-byte aligned")
+    d = _lib.RankDesc(nq, nt, D, slices)
+    lib = _lib.load()
+    before = torch.empty(nq, dtype=torch.int32, device=q.device)
+    tied = torch.empty(nq, dtype=torch.int32, device=q.device)
+    pos_d2 = torch.empty(nq, dtype=torch.float32, device=q.device)
+    ws_bytes = int(lib.focal_rank_workspace(C.byref(d)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+    check(lib.focal_rank_positive(C.byref(d), _p(q), _p(t), _p(t_sq), _p(pos), _p(before), _p(tied), _p(pos_d2), _p(ws), ws_bytes,
+                                  _stream()))
+    return (before, tied, pos_d2) if want_d2 else (before, tied)
+
+
 def kmeans_check_limits(D, K, R):
     """The limits of focal_kmeans_assign / focal_kmeans_update on the feature width, the clusters per restart and the restarts, refused
     here with the limit named (the library refuses them too, before any launch)."""

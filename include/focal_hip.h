@@ -694,6 +694,22 @@ int focal_knn_search(const focal_knn_desc* d, const float* q, const float* t, co
                      void* stream);
 int focal_knn_vote(const focal_knn_desc* d, const float* part_d2, const int* part_idx, const long* t_labels, const long* q_labels,
                    long* preds, int* nbr_idx, float* nbr_d2, int* conf, void* stream);
+/* Rank of one named gallery row per query (train_utils/retrieval.py: cross_modal_ranks, src/eval_retrieval.py): q fp32 [nq, D], t fp32
+ * [nt, D], t_sq fp32 [nt] = the gallery rows' squared norms as the caller computed them (|q|^2 is taken in the kernel), pos int [nq].
+ * d2(i, j) = (|q_i|^2 + t_sq[j]) - 2 q_i.t_j is the very bits focal_knn_search produces for that pair.  With p = pos[i] in [0, nt) and
+ * key the search's order-preserving key of a distance: pos_d2[i] = d2(i, p); before[i] = the j != p whose (key(d2(i, j)), j) orders
+ * before (key(d2(i, p)), p) -- the search's (d2, index) order, so the rank is before + 1 and a NaN distance orders behind every number;
+ * tied[i] = the j != p with key(d2(i, j)) == key(d2(i, p)).  A pos[i] outside [0, nt) gives before = tied = -1 and pos_d2 = NaN and
+ * never indexes t or t_sq.  tied and pos_d2 may be NULL.  The outputs are written, not accumulated, and are bit-identical for every
+ * `slices` (contiguous slices of ceil(nt / slices) gallery rows, as in the search).  Two launches -- the positives' distances from the
+ * gathered rows t[pos], then the scan, whose per-slice counts meet in integer atomics -- with no allocation, no host read and no
+ * floating-point atomic: the call can be captured.  The [nq, nt] distances exist in LDS tiles only.  ws: focal_rank_workspace(d) bytes.
+ * Limits (FOCAL_EINVAL before any launch): D >= 4, D % 4 == 0, nq, nt >= 1, 1 <= slices <= 65535, q and t 16-byte aligned,
+ * ws_bytes >= focal_rank_workspace(d). */
+typedef struct { int nq, nt, D, slices; } focal_rank_desc;
+size_t focal_rank_workspace(const focal_rank_desc* d);
+int focal_rank_positive(const focal_rank_desc* d, const float* q, const float* t, const float* t_sq, const int* pos, int* before, int* tied,
+                        float* pos_d2, void* ws, size_t ws_bytes, void* stream);
 /* K-means on the same features (train_utils/kmeans.py: GpuKMeans, src/eval_cluster.py): R restarts of K centroids are ONE matrix c fp32
  * [R*K, D], restart r in rows r*K .. r*K + K - 1, with c_sq fp32 [R*K] their squared norms; x is fp32 [n, D].  One Lloyd iteration of all
  * restarts is focal_kmeans_assign + focal_kmeans_update: three launches, no allocation, no host read (capturable), x read twice while
