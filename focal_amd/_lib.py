@@ -162,6 +162,15 @@ class RankDesc(C.Structure):
 RANK_MAX_SLICES = 65535
 
 
+class PairSumDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("nq", "nt", "D", "G", "slices", "fn", "self_offset")] + [("scale", C.c_float)]
+
+
+# focal_pair_sums: the functions of the squared distance, the largest G and the largest `slices` (include/focal_hip.h)
+PAIR_FNS = {"sqdist": 0, "dist": 1, "gauss": 2}
+PAIR_MAX_GROUPS, PAIR_MAX_SLICES = 64, 65535
+
+
 class KMeansDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n", "D", "K", "R", "slices")]
 
@@ -276,6 +285,8 @@ PROTOTYPES = {
     "focal_knn_vote": (C.c_int, [C.POINTER(KnnDesc), P, P, P, P, P, P, P, P, P]),
     "focal_rank_workspace": (C.c_size_t, [C.POINTER(RankDesc)]),
     "focal_rank_positive": (C.c_int, [C.POINTER(RankDesc), P, P, P, P, P, P, P, P, C.c_size_t, P]),
+    "focal_pair_sums_workspace": (C.c_size_t, [C.POINTER(PairSumDesc)]),
+    "focal_pair_sums": (C.c_int, [C.POINTER(PairSumDesc), P, P, P, P, P, P, C.c_size_t, P]),
     "focal_kmeans_assign": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P]),
     "focal_kmeans_update_workspace": (C.c_size_t, [C.POINTER(KMeansDesc)]),
     "focal_kmeans_update": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P, P, C.c_size_t, P]),

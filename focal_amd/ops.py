@@ -1441,6 +1441,73 @@ def rank_positive(q, t, t_sq, pos, slices=None, want_d2=False):
     return (before, tied, pos_d2) if want_d2 else (before, tied)
 
 
+_PAIR_WS = {}
+
+
+def pair_sums_check_limits(D, nq, nt, G, slices, fn, scale, self_offset):
+    """The limits of focal_pair_sums on the feature width, the row counts, the groups, the slices, the function and its scale, refused
+    here with the library's own text (it refuses them too, before any launch).  Returns the function's code."""
+    if D < 4 or D % 4:
+        raise _lib.FocalHipError(f"pair_sums: need D >= 4 and D % 4 == 0 (got D={D})")
+    if nq < 1 or nt < 1:
+        raise _lib.FocalHipError(f"pair_sums: need nq >= 1 and nt >= 1 (got nq={nq} nt={nt})")
+    if not 1 <= G <= _lib.PAIR_MAX_GROUPS:
+        raise _lib.FocalHipError(f"pair_sums: need 1 <= G <= {_lib.PAIR_MAX_GROUPS} (got G={G})")
+    if not 1 <= slices <= _lib.PAIR_MAX_SLICES:
+        raise _lib.FocalHipError(f"pair_sums: need 1 <= slices <= {_lib.PAIR_MAX_SLICES} (got slices={slices})")
+    code = _lib.PAIR_FNS.get(fn, fn if isinstance(fn, int) else -1)
+    if code not in _lib.PAIR_FNS.values():
+        raise _lib.FocalHipError(f"pair_sums: need fn in 0 .. 2 (sqdist, dist, gauss; got fn={fn})")
+    if not (math.isfinite(scale) and scale >= 0):
+        raise _lib.FocalHipError(f"pair_sums: need a finite scale >= 0 (got scale={scale:g})")
+    if self_offset < -1:
+        raise _lib.FocalHipError(f"pair_sums: need self_offset >= -1 (got self_offset={self_offset})")
+    return code
+
+
+def pair_sums(q, t, t_sq, group=None, G=1, fn="dist", scale=1.0, self_offset=None, slices=None):
+    """S fp32 [nq, G]: S[i, g] = the sum over the rows j of t (fp32 [nt, D], squared norms t_sq [nt]) with group[j] == g of
+    f(max(d2(q_i, t_j), 0)) under focal_knn_search's distance (focal_pair_sums: one or two launches, no host read, no [nq, nt] tensor).
+    fn: "sqdist" (f = x), "dist" (sqrt x) or "gauss" (exp(-scale x)).  group: int32 [nt], ids outside [0, G) are not counted; None with
+    G = 1 puts every row in group 0.  self_offset = o says that q[i] is t[o + i] and leaves that one candidate out (None: nothing).
+    Equal arguments give equal bits; `slices` (None: knn_default_slices) fixes the order of the sums, so another value may differ in
+    the last bits."""
+    _need_cuda(q, t, t_sq, group)
+    if q.dtype != torch.float32 or t.dtype != torch.float32 or t_sq.dtype != torch.float32 or q.dim() != 2 or t.dim() != 2:
+        raise _lib.FocalHipError("pair_sums: q, t and t_sq are fp32, q and t matrices")
+    nq, D = q.shape
+    nt = t.shape[0]
+    if t.shape[1] != D or t_sq.numel() != nt:
+        raise _lib.FocalHipError(f"pair_sums: q {tuple(q.shape)} against t {tuple(t.shape)} and {t_sq.numel()} norms")
+    if group is not None and (group.dtype != torch.int32 or group.numel() != nt):
+        raise _lib.FocalHipError(f"pair_sums: {group.numel()} {group.dtype} group ids for {nt} rows (need int32 [nt])")
+    if not (q.is_contiguous() and t.is_contiguous() and t_sq.is_contiguous() and (group is None or group.is_contiguous())):
+        raise _lib.FocalHipError("pair_sums: q, t, t_sq and group must be contiguous")
+    G = int(G)
+    if group is None and G != 1:
+        raise _lib.FocalHipError(f"pair_sums: G={G} groups need the group ids (group may be None for G = 1 only)")
+    if nq >= 1 and nt >= 1 and slices is None:
+        slices = knn_default_slices(nq, nt, q.device)
+    slices = 1 if slices is None else int(slices)
+    self_offset = -1 if self_offset is None else int(self_offset)
+    code = pair_sums_check_limits(D, nq, nt, G, slices, fn, float(scale), self_offset)
+    if q.data_ptr() % 16 or t.data_ptr() % 16:
+        raise _lib.FocalHipError("pair_sums: q and t must be 16-byte aligned")
+    d = _lib.PairSumDesc(nq, nt, D, G, slices, code, self_offset, float(scale))
+    lib = _lib.load()
+    need = int(lib.focal_pair_sums_workspace(C.byref(d)))
+    if need == 0:
+        raise _lib.FocalHipError(f"pair_sums: {lib.focal_last_error().decode()}")
+    key = (q.device, torch.cuda.current_stream().cuda_stream)
+    ws = _PAIR_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        _PAIR_WS[key] = ws
+    S = torch.empty(nq, G, dtype=torch.float32, device=q.device)
+    check(lib.focal_pair_sums(C.byref(d), _p(q), _p(t), _p(t_sq), _p(group), _p(S), _p(ws), ws.numel(), _stream()))
+    return S
+
+
 def kmeans_check_limits(D, K, R):
     """The limits of focal_kmeans_assign / focal_kmeans_update on the feature width, the clusters per restart and the restarts, refused
     here with the limit named (the library refuses them too, before any launch)."""

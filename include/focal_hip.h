@@ -710,6 +710,27 @@ typedef struct { int nq, nt, D, slices; } focal_rank_desc;
 size_t focal_rank_workspace(const focal_rank_desc* d);
 int focal_rank_positive(const focal_rank_desc* d, const float* q, const float* t, const float* t_sq, const int* pos, int* before, int* tied,
                         float* pos_d2, void* ws, size_t ws_bytes, void* stream);
+/* Sums of a function of the distance over all pairs (train_utils/geometry.py: silhouette, uniformity; src/eval_geometry.py): q fp32
+ * [nq, D], t fp32 [nt, D], t_sq fp32 [nt] as for focal_rank_positive, group int [nt] (NULL with G = 1: every row is in group 0), S fp32
+ * [nq, G].  S[i, g] = sum over the j with group[j] == g and j != self_offset + i of f(max(d2(i, j), 0)), d2 the very bits
+ * focal_knn_search produces for that pair; f = x (FOCAL_PAIR_SQDIST), sqrt(x) (FOCAL_PAIR_DIST) or exp(-scale x) (FOCAL_PAIR_GAUSS).
+ * self_offset >= 0 says that query row i IS gallery row self_offset + i: that one candidate is left out by its index (a duplicate of
+ * the row elsewhere still counts); -1 leaves nothing out.  A group[j] outside [0, G) means row j is not counted; a group without rows
+ * gets exactly 0; a non-finite term of a counted row makes its sum non-finite and may make the query's other groups' sums NaN, an uncounted
+ * row reaches no sum.  The gallery is cut into `slices` contiguous slices of ceil(nt / slices) rows; each
+ * (128 queries, slice) workgroup writes its partial [128, G] to ws and a second launch adds the partials in slice order (one slice: one
+ * launch that writes S).  No floating-point atomic: the order of every addition is fixed by (nq, nt, D, G, slices), so equal arguments
+ * give equal bits; another `slices` is another order and may differ in the last bits.  S is written, not accumulated.  No allocation, no
+ * host read: the call can be captured.  The [nq, nt] distances exist in LDS tiles only.  ws: focal_pair_sums_workspace(d) bytes (never
+ * 0 for a valid descriptor).  Limits (FOCAL_EINVAL before any launch): D >= 4, D % 4 == 0, nq, nt >= 1, 1 <= G <= 64, group non-NULL
+ * unless G = 1, 1 <= slices <= 65535, ceil(nq / 128) * slices and nq * G / 256 within the launch grid, fn one of the three, scale finite
+ * and >= 0, self_offset >= -1, q and t 16-byte aligned, ws_bytes >= focal_pair_sums_workspace(d). */
+enum { FOCAL_PAIR_SQDIST = 0, FOCAL_PAIR_DIST = 1, FOCAL_PAIR_GAUSS = 2 };
+#define FOCAL_PAIR_MAX_GROUPS 64
+typedef struct { int nq, nt, D, G, slices, fn, self_offset; float scale; } focal_pairsum_desc;
+size_t focal_pair_sums_workspace(const focal_pairsum_desc* d);
+int focal_pair_sums(const focal_pairsum_desc* d, const float* q, const float* t, const float* t_sq, const int* group, float* S, void* ws,
+                    size_t ws_bytes, void* stream);
 /* K-means on the same features (train_utils/kmeans.py: GpuKMeans, src/eval_cluster.py): R restarts of K centroids are ONE matrix c fp32
  * [R*K, D], restart r in rows r*K .. r*K + K - 1, with c_sq fp32 [R*K] their squared norms; x is fp32 [n, D].  One Lloyd iteration of all
  * restarts is focal_kmeans_assign + focal_kmeans_update: three launches, no allocation, no host read (capturable), x read twice while
