@@ -171,6 +171,16 @@ PAIR_FNS = {"sqdist": 0, "dist": 1, "gauss": 2}
 PAIR_MAX_GROUPS, PAIR_MAX_SLICES = 64, 65535
 
 
+class SeqRankDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n", "D", "L", "slices", "fn")] + [("margin", C.c_float)]
+
+
+# focal_seq_rank: the sequence lengths (blocks never straddle a 64-row tile), the two functions and the largest `slices` (include/focal_hip.h)
+SEQRANK_LENGTHS = (2, 4, 8, 16)
+SEQRANK_FNS = {"sqdist": 0, "dist": 1}
+SEQRANK_MAX_SLICES = 65535
+
+
 class KMeansDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n", "D", "K", "R", "slices")]
 
@@ -287,6 +297,8 @@ PROTOTYPES = {
     "focal_rank_positive": (C.c_int, [C.POINTER(RankDesc), P, P, P, P, P, P, P, P, C.c_size_t, P]),
     "focal_pair_sums_workspace": (C.c_size_t, [C.POINTER(PairSumDesc)]),
     "focal_pair_sums": (C.c_int, [C.POINTER(PairSumDesc), P, P, P, P, P, P, C.c_size_t, P]),
+    "focal_seq_rank_workspace": (C.c_size_t, [C.POINTER(SeqRankDesc)]),
+    "focal_seq_rank": (C.c_int, [C.POINTER(SeqRankDesc), P, P, P, P, P, P, P, P, P, C.c_size_t, P]),
     "focal_kmeans_assign": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P]),
     "focal_kmeans_update_workspace": (C.c_size_t, [C.POINTER(KMeansDesc)]),
     "focal_kmeans_update": (C.c_int, [C.POINTER(KMeansDesc), P, P, P, P, P, P, P, P, C.c_size_t, P]),

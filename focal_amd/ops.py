@@ -1508,6 +1508,67 @@ def pair_sums(q, t, t_sq, group=None, G=1, fn="dist", scale=1.0, self_offset=Non
     return S
 
 
+def seq_rank_check_limits(D, n, L, slices, fn, margin):
+    """The limits of focal_seq_rank on the feature width, the sequence length, the row count, the slices, the function and the margin,
+    refused here with the library's own text (it refuses them too, before any launch).  Returns the function's code."""
+    if D < 4 or D % 4:
+        raise _lib.FocalHipError(f"seq_rank: need D >= 4 and D % 4 == 0 (got D={D})")
+    if L not in _lib.SEQRANK_LENGTHS:
+        raise _lib.FocalHipError(f"seq_rank: need L in {{2, 4, 8, 16}} (got L={L})")
+    if n < 1 or n % L:
+        raise _lib.FocalHipError(f"seq_rank: need n % L == 0 (got n={n} L={L})")
+    if n // L < 2:
+        raise _lib.FocalHipError(f"seq_rank: need S = n / L >= 2 sequences (got n={n} L={L})")
+    if not 1 <= slices <= _lib.SEQRANK_MAX_SLICES:
+        raise _lib.FocalHipError(f"seq_rank: need 1 <= slices <= {_lib.SEQRANK_MAX_SLICES} (got slices={slices})")
+    if -(-n // _lib.KNN_QUERY_TILE) * slices >= 1 << 31:
+        raise _lib.FocalHipError(f"seq_rank: n / {_lib.KNN_QUERY_TILE} * slices exceeds the launch grid (n={n} slices={slices})")
+    code = _lib.SEQRANK_FNS.get(fn, fn if isinstance(fn, int) else -1)
+    if code not in _lib.SEQRANK_FNS.values():
+        raise _lib.FocalHipError(f"seq_rank: need fn in 0 .. 1 (sqdist, dist; got fn={fn})")
+    if not math.isfinite(margin):
+        raise _lib.FocalHipError(f"seq_rank: need a finite margin (got margin={margin:g})")
+    return code
+
+
+def seq_rank(z, z_sq, L, margin, fn="dist", slices=None):
+    """The sequence ranking counts of z (fp32 [n, D], rows a L .. a L + L - 1 = sequence a, squared norms z_sq [n]) under
+    focal_knn_search's distance (focal_seq_rank: two or three launches, no host read, no [n, n] and no [S, S] tensor).  Returns the dict
+    intra_d2 (fp32 [n, L]), intra_sum, hinge_sum, inter_sum (fp32 [S]), before, viol (int32 [S]) of include/focal_hip.h.  fn: "sqdist"
+    (f = x) or "dist" (sqrt x).  The integer counts do not depend on `slices` (None: knn_default_slices); it fixes the order of the float
+    sums, so another value may differ in their last bits."""
+    _need_cuda(z, z_sq)
+    if z.dtype != torch.float32 or z_sq.dtype != torch.float32 or z.dim() != 2:
+        raise _lib.FocalHipError("seq_rank: z and z_sq are fp32, z a matrix")
+    n, D = z.shape
+    if z_sq.numel() != n:
+        raise _lib.FocalHipError(f"seq_rank: z {tuple(z.shape)} and {z_sq.numel()} norms")
+    if not (z.is_contiguous() and z_sq.is_contiguous()):
+        raise _lib.FocalHipError("seq_rank: z and z_sq must be contiguous")
+    L = int(L)
+    if n >= 1 and slices is None:
+        slices = knn_default_slices(n, n, z.device)
+    slices = 1 if slices is None else int(slices)
+    code = seq_rank_check_limits(D, n, L, slices, fn, float(margin))
+    if z.data_ptr() % 16:
+        raise _lib.FocalHipError("seq_rank: z must be 16-byte aligned")
+    d = _lib.SeqRankDesc(n, D, L, slices, code, float(margin))
+    lib = _lib.load()
+    need = int(lib.focal_seq_rank_workspace(C.byref(d)))
+    if need == 0:
+        raise _lib.FocalHipError(f"seq_rank: {lib.focal_last_error().decode()}")
+    S = n // L
+    out = {"intra_d2": torch.empty(n, L, dtype=torch.float32, device=z.device)}
+    for name in ("intra_sum", "hinge_sum", "inter_sum"):
+        out[name] = torch.empty(S, dtype=torch.float32, device=z.device)
+    for name in ("before", "viol"):
+        out[name] = torch.empty(S, dtype=torch.int32, device=z.device)
+    ws = torch.empty(need, dtype=torch.uint8, device=z.device)
+    check(lib.focal_seq_rank(C.byref(d), _p(z), _p(z_sq), _p(out["intra_d2"]), _p(out["intra_sum"]), _p(out["before"]), _p(out["viol"]),
+                             _p(out["hinge_sum"]), _p(out["inter_sum"]), _p(ws), need, _stream()))
+    return out
+
+
 def kmeans_check_limits(D, K, R):
     """The limits of focal_kmeans_assign / focal_kmeans_update on the feature width, the clusters per restart and the restarts, refused
     here with the limit named (the library refuses them too, before any launch)."""

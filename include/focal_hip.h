@@ -731,6 +731,27 @@ typedef struct { int nq, nt, D, G, slices, fn, self_offset; float scale; } focal
 size_t focal_pair_sums_workspace(const focal_pairsum_desc* d);
 int focal_pair_sums(const focal_pairsum_desc* d, const float* q, const float* t, const float* t_sq, const int* group, float* S, void* ws,
                     size_t ws_bytes, void* stream);
+/* Sequence ranking counts of the temporal constraint (train_utils/temporal.py: sequence_ranking; src/eval_temporal.py): z fp32 [n, D]
+ * with n = S L, rows a L .. a L + L - 1 = sequence a, z_sq fp32 [n] as for focal_rank_positive.  d2(i, j) is the very bits
+ * focal_knn_search produces for that pair, f = x (FOCAL_PAIR_SQDIST) or sqrt(x) (FOCAL_PAIR_DIST) of max(d2, 0).
+ * intra_d2 [n, L]: d2(i, a(i) L + c), self column included.  intra_sum [S]: sum over i != j in a of f, added in row-major (i, j) order.
+ * With P(a, b) = sum over i in a, j in b of f, added in row-major order inside the block:
+ * before [S] (int): the b != a with P(a, b) (L^2 - L) < intra_sum[a] L^2 -- the mean block distance below the mean intra distance;
+ * viol [S] (int): the same with margin L^2 (L^2 - L) added to the right-hand side -- the loss's hinge active for (a, b);
+ * hinge_sum [S]: sum over b != a of max(0, intra_sum[a] / (L^2 - L) - P(a, b) / L^2 + margin), carried as the difference of viol's two
+ * sides and divided by L^2 (L^2 - L) once, after the last addition; inter_sum [S]: sum over b != a of P(a, b).
+ * The block b = a is left out by index.  A NaN pooled value is never counted and makes that sequence's two float sums NaN.  Every output
+ * is written, not accumulated.  z is cut into `slices` contiguous slices of whole 64-row tiles; the integer counts meet in integer
+ * atomics and are bit-identical for every `slices`; the float partials go to ws and a last launch adds them in slice order (one slice:
+ * the scan writes them itself), so equal arguments give equal bits and another `slices` may differ in the last bits.  No floating-point
+ * atomic, no allocation, no host read: the call can be captured.  The [n, n] distances and the [S, S] pooled values exist in LDS tiles
+ * and registers only.  ws: focal_seq_rank_workspace(d) bytes (never 0 for a valid descriptor).  Limits (FOCAL_EINVAL before any
+ * launch): D >= 4, D % 4 == 0, L in {2, 4, 8, 16}, n % L == 0, S >= 2, 1 <= slices <= 65535, ceil(n / 128) * slices within the launch
+ * grid, fn one of the two, margin finite, z 16-byte aligned, ws_bytes >= focal_seq_rank_workspace(d). */
+typedef struct { int n, D, L, slices, fn; float margin; } focal_seqrank_desc;
+size_t focal_seq_rank_workspace(const focal_seqrank_desc* d);
+int focal_seq_rank(const focal_seqrank_desc* d, const float* z, const float* z_sq, float* intra_d2, float* intra_sum, int* before, int* viol,
+                   float* hinge_sum, float* inter_sum, void* ws, size_t ws_bytes, void* stream);
 /* K-means on the same features (train_utils/kmeans.py: GpuKMeans, src/eval_cluster.py): R restarts of K centroids are ONE matrix c fp32
  * [R*K, D], restart r in rows r*K .. r*K + K - 1, with c_sq fp32 [R*K] their squared norms; x is fp32 [n, D].  One Lloyd iteration of all
  * restarts is focal_kmeans_assign + focal_kmeans_update: three launches, no allocation, no host read (capturable), x read twice while
