@@ -213,6 +213,14 @@ class AdamWDesc(C.Structure):
 # words of the record {steps, clipped, skipped, sum of norms, max norm, last norm, last sum of squares, last coef}
 CLIP_MAX_SEGMENTS, MAX_BLOCKS, CLIP_SCRATCH_WORDS, CLIP_RECORD_WORDS = 8, 1024, 1024, 8
 
+# LAMB (include/focal_hip.h: focal_lamb_multi): elements of one workgroup's piece, words of the per-tensor record {phi, |w|, |u|}, tensor flags
+LAMB_PIECE, LAMB_RECORD_WORDS, LAMB_ADAPT, LAMB_DECAY = 8192, 3, 1, 2
+
+
+class LambTable(C.Structure):
+    _fields_ = [("host", C.c_void_p), ("dev", C.c_void_p), ("npieces", C.c_int), ("ntensors", C.c_int), ("partials", C.c_void_p),
+                ("partial_words", C.c_int), ("record", C.c_void_p), ("record_words", C.c_int)]
+
 
 class TraceRecord(C.Structure):
     _fields_ = [("kernel", C.c_char * 384), ("grid", C.c_uint * 3), ("block", C.c_uint * 3), ("stream", C.c_void_p), ("us", C.c_float)]
@@ -329,6 +337,11 @@ PROTOTYPES = {
     "focal_adamw_clip_multi_advance": (C.c_int, [C.POINTER(AdamWDesc), C.c_int, C.POINTER(P), C.POINTER(P), C.POINTER(P),
                                                  C.POINTER(P), C.POINTER(P), C.POINTER(C.c_long), P, P, C.c_int, P, P, C.c_int, P, C.c_int,
                                                  C.c_float, P]),
+    "focal_lamb_multi": (C.c_int, [C.POINTER(AdamWDesc), C.c_int, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P),
+                                   C.POINTER(C.c_long), C.POINTER(LambTable), C.c_float, P, P, P, C.c_int, P, C.c_int, C.c_float, P]),
+    "focal_lamb_multi_advance": (C.c_int, [C.POINTER(AdamWDesc), C.c_int, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P),
+                                           C.POINTER(C.c_long), C.POINTER(LambTable), C.c_float, P, P, C.c_int, P, P, C.c_int, P, C.c_int,
+                                           C.c_float, P]),
     "focal_cast_bf16": (C.c_int, [P, P, C.c_long, P]),
     "focal_conv_in_fwd": (C.c_int, [C.POINTER(ConvInDesc), P, P, P, P, P]),
     "focal_conv_in_bwd_weight": (C.c_int, [C.POINTER(ConvInDesc), P, P, C.c_int, P, P, P]),

@@ -186,6 +186,72 @@ def adamw_multi(segments, lr_dev, rng_state, beta1=0.9, beta2=0.999, eps=1e-8, w
                                         lens, _p(lr_dev), _p(rng_state), _stream()))
 
 
+def lamb_table(index_rows, lo, hi, exclude_1d=True):
+    """The piece table of LAMB over the arena span [lo, hi), host side (pure Python).  index_rows: the (offset, numel, shape) rows of
+    ParamArena.index in arena order.  Every tensor whose offset lies in the span is cut into pieces of at most _lib.LAMB_PIECE elements
+    that tile its ALIGN-padded extent (the pad elements are zero and stay zero); offsets count from `lo`.  exclude_1d: a tensor with
+    ndim <= 1 is neither adapted nor decayed.  Returns {"n", "pieces": [(offset, length, tensor)], "tensors": [(first piece, last piece,
+    flags)], "rows": [the index row of each tensor]} -- tensors without elements own no piece and are left out."""
+    rows = [(int(o), int(k), tuple(shp)) for o, k, shp in index_rows]
+    inside = [(i, r) for i, r in enumerate(rows) if lo <= r[0] < hi and r[1] > 0]
+    pieces, tensors, which = [], [], []
+    for j, (i, (o, k, shp)) in enumerate(inside):
+        end = inside[j + 1][1][0] if j + 1 < len(inside) else hi  # the padded extent ends where the next tensor starts
+        if not (o + k <= end <= hi and (o - lo) % 4 == 0 and (end - o) % 4 == 0):
+            raise ValueError(f"lamb_table: tensor {i} at [{o}, {o + k}) does not fit a padded extent ending at {end} inside [{lo}, {hi})")
+        flags = 0 if (exclude_1d and len(shp) <= 1) else (_lib.LAMB_ADAPT | _lib.LAMB_DECAY)
+        first = len(pieces)
+        for a in range(o, end, _lib.LAMB_PIECE):
+            pieces.append((a - lo, min(_lib.LAMB_PIECE, end - a), len(tensors)))
+        tensors.append((first, len(pieces), flags))
+        which.append(i)
+    return {"n": hi - lo, "pieces": pieces, "tensors": tensors, "rows": which}
+
+
+def lamb_table_upload(table, device):
+    """The device side of a lamb_table(): the table's words, the partial row and the per-tensor record (call outside graph capture)."""
+    words = [w for o, k, t in table["pieces"] for w in (o, k, t, 0)] + [w for a, b, f in table["tensors"] for w in (a, b, f, 0)]
+    out = dict(table)
+    out["host"] = (C.c_int32 * max(len(words), 1))(*words)
+    out["dev"] = torch.tensor(words, dtype=torch.int32).to(device)
+    out["partials"] = torch.zeros(2 * max(len(table["pieces"]), 1), dtype=torch.float32, device=device)
+    out["record"] = torch.zeros(_lib.LAMB_RECORD_WORDS * max(len(table["tensors"]), 1), dtype=torch.float32, device=device)
+    return out
+
+
+def lamb_multi(segments, tables, lr_dev, rng_state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.05, max_trust=math.inf, advance=False,
+               seed_state=None, clip=None):
+    """LAMB over `segments` (as adamw_multi: (p, g, m, v, shadow_or_None) flat tensors), tables[i] the uploaded lamb_table of segment i
+    (its offsets count from the segment's start).  Two launches per segment: moments + per-piece sums of squares, then the trust ratio
+    and the weights; the per-tensor {phi, |w|, |u|} lands in tables[i]["record"].  advance / seed_state / clip: as adamw_multi."""
+    n = len(segments)
+    max_trust = float(max_trust)
+    if not max_trust > 0.0:
+        raise ValueError(f"lamb_multi: max_trust = {max_trust} must be positive (inf: no clamp)")
+    if len(tables) != n:
+        raise ValueError(f"lamb_multi: {len(tables)} tables for {n} segments")
+    arr = lambda i: (C.c_void_p * max(n, 1))(*[_p(s[i]) for s in segments])
+    has_shadow = any(s[4] is not None for s in segments)
+    lens = (C.c_long * max(n, 1))(*[s[0].numel() for s in segments])
+    tabs = (_lib.LambTable * max(n, 1))(*[_lib.LambTable(C.cast(t["host"], C.c_void_p), _p(t["dev"]), len(t["pieces"]), len(t["tensors"]),
+                                                        _p(t["partials"]), t["partials"].numel(), _p(t["record"]), t["record"].numel())
+                                          for t in tables])
+    d = AdamWDesc(beta1, beta2, eps, weight_decay, 0)
+    if clip is not None:
+        (row, rec), max_norm = clip
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:
+            raise ValueError(f"lamb_multi: max_norm = {max_norm} must be positive (inf: clip nothing, record the norms)")
+        tail = (_p(row), row.numel(), _p(rec), rec.numel(), max_norm, _stream())
+    else:
+        tail = (None, 0, None, 0, 0.0, _stream())
+    head = (C.byref(d), n, arr(0), arr(1), arr(2), arr(3), arr(4) if has_shadow else None, lens, tabs, max_trust, _p(lr_dev), _p(rng_state))
+    if advance:
+        check(_lib.load().focal_lamb_multi_advance(*head, rng_state.numel(), _p(seed_state), *tail))
+        return
+    check(_lib.load().focal_lamb_multi(*head, *tail))
+
+
 # ------------------------------------------------------------------------------------------------ row 3
 _TWIDDLES = {}
 

@@ -3,6 +3,7 @@
 Keeps the torch.optim.Optimizer surface the reference loop and timm-style schedulers use (`param_groups[i]["lr"]`,
 `zero_grad()`, `step()`), but `step()` is one streaming HIP kernel over the arena's hot region; parameters whose
 `.grad` is None (frozen patch embedding, unused heads) are skipped entirely, exactly as torch does.
+`FocalLAMB` is the same surface with LAMB's per-tensor trust ratios on AdamW's state (two launches per arena).
 """
 import torch
 
@@ -140,10 +141,14 @@ class FocalAdamW(torch.optim.Optimizer):
                 self._clip_state = ops.new_clip_state(dev)
             ops.grad_norm([s[1] for s in segs], self._clip_state)
             clip = (self._clip_state, self.max_grad_norm)
-        ops.adamw_multi(segs, self._lr_dev, self._step_state, g0["betas"][0], g0["betas"][1], g0["eps"],
-                        g0["weight_decay"], self._l2, advance=True, seed_state=runtime.rng_state(dev), clip=clip)
+        self._update(arenas, segs, g0, clip, dev)
         for ar in arenas:
             ar.mark_shadow_fresh()
+
+    def _update(self, arenas, segs, g0, clip, dev):
+        """The update launches of step(): segs[i] = (w, g, m, v, shadow) of arenas[i]'s span."""
+        ops.adamw_multi(segs, self._lr_dev, self._step_state, g0["betas"][0], g0["betas"][1], g0["eps"],
+                        g0["weight_decay"], self._l2, advance=True, seed_state=runtime.rng_state(dev), clip=clip)
 
     def clip_stats(self):
         """Gradient-norm statistics since the last call (one device-to-host copy; the record is reset), or None with clipping off or
@@ -175,3 +180,58 @@ class FocalAdamW(torch.optim.Optimizer):
         if self._step_state is None:
             self._step_state = ops.new_step_state(dev)
         self._step_state[1] = int(state["step"])
+
+
+class FocalLAMB(FocalAdamW):
+    """LAMB (You et al. 2020, Algorithm 2) over the arena, with AdamW's conventions and AdamW's state (m, v, the device step count): a
+    "layer" is one tensor of ParamArena.index inside the optimizer's span,
+        u = r + wd * w,  phi = |w| / |u| (1 where a norm is zero or not finite, or the tensor is not adapted),  w -= lr * min(phi, max_trust) * u
+    in two launches per arena (ops.lamb_multi).  exclude_1d (the published BERT recipe): tensors with ndim <= 1 -- biases, norm scales and
+    shifts -- are neither adapted nor decayed.  Everything else -- zero_grad, sync_lr, the reductions, clipping, train_state -- is FocalAdamW's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, exclude_1d=True, max_trust=float("inf")):
+        if not isinstance(exclude_1d, bool):
+            raise ValueError(f"FocalLAMB: exclude_1d = {exclude_1d!r} must be a bool")
+        max_trust = float(max_trust)
+        if not max_trust > 0.0:
+            raise ValueError(f"FocalLAMB: max_trust = {max_trust} must be positive (inf: no clamp)")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, l2_decay=False, max_grad_norm=max_grad_norm)
+        self.exclude_1d = exclude_1d
+        self.max_trust = max_trust
+        self._tables = {}  # (arena, span) -> (arena, uploaded ops.lamb_table)
+
+    def _table(self, ar, lo, hi):
+        key = (id(ar), lo, hi)
+        hit = self._tables.get(key)
+        if hit is None or hit[0] is not ar:
+            if torch.cuda.is_current_stream_capturing():
+                raise ops._lib.FocalHipError("FocalLAMB: the piece table is uploaded outside graph capture (run one eager step first)")
+            hit = self._tables[key] = (ar, ops.lamb_table_upload(ops.lamb_table(ar.index.values(), lo, hi, self.exclude_1d), ar.device))
+        return hit[1]
+
+    def _update(self, arenas, segs, g0, clip, dev):
+        # (a segment is the arena's flat buffer cut to the span: its storage offset is the span's start)
+        tables = [self._table(ar, s[0].storage_offset(), s[0].storage_offset() + s[0].numel()) for ar, s in zip(arenas, segs)]
+        ops.lamb_multi(segs, tables, self._lr_dev, self._step_state, g0["betas"][0], g0["betas"][1], g0["eps"], g0["weight_decay"],
+                       max_trust=self.max_trust, advance=True, seed_state=runtime.rng_state(dev), clip=clip)
+
+    def trust_stats(self):
+        """The trust ratios of the last step that was not skipped (one device-to-host copy), or None before the first step:
+        {tensors, min, min_name, median, max, max_name} over the adapted tensors (all of them if none is adapted), and "phi": {name: phi}."""
+        arenas = self._arenas()
+        live = [(ar, t) for ar, t in self._tables.values() if any(ar is a for a in arenas)]
+        if not live or self._step_state is None:
+            return None
+        rec = torch.cat([t["record"] for _, t in live]).cpu().view(-1, ops._lib.LAMB_RECORD_WORDS)
+        names, adapted = [], []
+        for ar, t in live:
+            keys = list(ar.index)
+            names += [keys[i] for i in t["rows"]]
+            adapted += [bool(f & ops._lib.LAMB_ADAPT) for _, _, f in t["tensors"]]
+        phi = rec[:len(names), 0].tolist()
+        pick = [i for i, a in enumerate(adapted) if a] or list(range(len(names)))
+        order = sorted(pick, key=lambda i: phi[i])
+        lo, hi, mid = order[0], order[-1], order[len(order) // 2]
+        median = phi[mid] if len(order) % 2 else 0.5 * (phi[order[len(order) // 2 - 1]] + phi[mid])
+        return {"tensors": len(order), "min": phi[lo], "min_name": names[lo], "median": median, "max": phi[hi], "max_name": names[hi],
+                "phi": dict(zip(names, phi))}

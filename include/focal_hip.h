@@ -935,6 +935,38 @@ int focal_adamw_clip_multi_advance(const focal_adamw_desc* d, int nseg, float* c
                                    float* const* v, void* const* shadow_bf16, const long* n, const float* lr_dev,
                                    uint32_t* step_state, int step_state_words, uint32_t* seed_state, const float* partials,
                                    int partial_words, uint32_t* record, int record_words, float max_norm, void* stream);
+/* LAMB (You et al. 2020, Algorithm 2) with AdamW's conventions -- the same bias correction, the same place for eps, the same device lr
+ * scalar and step count, the same m / v state --: per tensor T of the arena
+ *     m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  r = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps);  u = r + lambda_T w
+ *     phi_T = |w_T| / |u_T| if T is adapted and both norms are positive and finite, else 1;  phi_T = min(phi_T, max_trust)
+ *     w -= lr phi_T u
+ * in two launches per segment over one grid, a workgroup per PIECE (at most FOCAL_LAMB_PIECE elements inside one tensor's padded extent):
+ * the first writes m, v and the piece's sum(w^2), sum(u^2) to partials[2 piece], [2 piece + 1]; in the second every workgroup adds its
+ * tensor's partials in one fixed order, forms phi_T and writes w and the bf16 shadow.  Plain stores, no floating-point atomics: bit-repeatable.
+ * g is not written.  d->weight_decay is lambda of the decayed tensors; d->l2_decay must be 0.
+ *   table: host = 4 * npieces + 4 * ntensors 32-bit words, {offset, length, tensor, 0} per piece (elements from the segment's start; lengths
+ *     positive multiples of 4 up to FOCAL_LAMB_PIECE, offsets multiples of 4, ascending, not overlapping, inside the segment), then
+ *     {first piece, last piece (exclusive), flags, 0} per tensor (the ranges partition the pieces in order; flags: 1 adapted, 2 decayed).
+ *     All of this is checked on `host` before a launch; dev = the same words in device memory (16-byte aligned), which the kernels read.
+ *   partials: 2 * npieces floats of scratch; record: FOCAL_LAMB_RECORD_WORDS floats per tensor, {phi_T, |w_T| before the update, |u_T|},
+ *     one writer per tensor and call.
+ *   clip_partials / clip_record (both null: no clipping): the row focal_grad_norm_multi left and the record of focal_adamw_clip_multi, with
+ *     the same meaning: the update runs on g * coef, a non-finite norm leaves w, m, v, the shadow, the LAMB record and the step count alone
+ *     and counts a skipped step.
+ *   _advance: the step count used is step_state[1] + 1 and the second launch of the last non-empty segment advances step_state and
+ *     seed_state, exactly as focal_adamw_multi_advance does. */
+#define FOCAL_LAMB_PIECE 8192
+#define FOCAL_LAMB_RECORD_WORDS 3
+typedef struct { const int32_t* host; const int32_t* dev; int npieces, ntensors; float* partials; int partial_words; float* record; int record_words; } focal_lamb_table;
+int focal_lamb_multi(const focal_adamw_desc* d, int nseg, float* const* p, const float* const* g, float* const* m, float* const* v,
+                     void* const* shadow_bf16, const long* n, const focal_lamb_table* tables, float max_trust, const float* lr_dev,
+                     const uint32_t* rng_state, const float* clip_partials, int clip_partial_words, uint32_t* clip_record,
+                     int clip_record_words, float max_norm, void* stream);
+int focal_lamb_multi_advance(const focal_adamw_desc* d, int nseg, float* const* p, const float* const* g, float* const* m,
+                             float* const* v, void* const* shadow_bf16, const long* n, const focal_lamb_table* tables, float max_trust,
+                             const float* lr_dev, uint32_t* step_state, int step_state_words, uint32_t* seed_state,
+                             const float* clip_partials, int clip_partial_words, uint32_t* clip_record, int clip_record_words,
+                             float max_norm, void* stream);
 /* fp32 -> bf16 cast of a weight segment (refreshing the shadow after load_state_dict) */
 int focal_cast_bf16(const float* src, void* dst, long n, void* stream);
 
