@@ -2,11 +2,11 @@
 // together is three launches -- assign, accumulate, finish -- with no floating-point atomic in any of them.
 //
 // focal_kmeans_assign: knn.hip's search with the training rows replaced by the R*K centroids and the k-best scan by a per-restart best.  A
-// workgroup owns KNN_BQ = 128 rows of x and walks ALL R*K centroid rows in tiles of KNN_BT = 64: the same exact-fp32 MFMA product on the
-// same staging, the same |x|^2 tree (knn_dist.hpp), d2 written to the same LDS tile and no further.  One thread per row scans the tile's
-// columns in order; column g belongs to restart g / K, so the thread carries ONE 64-bit best, (key of d2) << 32 | k, and hands it in when
-// the column counter reaches K -- whether or not a tile boundary fell inside the restart.  d2 of a (row, centroid) pair is the function
-// focal_knn_search computes, so for R = 1 the labels are its nearest neighbour bit for bit.
+// workgroup owns KNN_BQ = 128 rows of x and walks ALL R*K centroid rows in tiles of KNN_BT = 64: knn_dist.hpp's PairTile, d2 written to
+// its LDS tile and no further.  One thread per row scans the tile's columns in order; column g belongs to restart g / K, so the thread
+// carries ONE 64-bit best, (key of d2) << 32 | k, and hands it in when the column counter reaches K -- whether or not a tile boundary
+// fell inside the restart.  d2 of a (row, centroid) pair is focal_knn_search's, so for R = 1 the labels are its nearest neighbour bit
+// for bit.
 // focal_kmeans_update: a workgroup owns one of `slices` contiguous row slices, 64 feature columns and a group of restarts whose
 // accumulators [restarts * K][64] fit in LDS.  Rows go through an LDS block of 64 rows x 64 columns; wave w takes the group's restarts
 // w, w + 4, ..: lane <-> column, rows in order, acc[label][lane] += x -- every accumulator cell belongs to one lane and sees its rows in
@@ -23,87 +23,37 @@ constexpr int KM_ACC_ROWS = 160;   // accumulator rows (restarts of a group x K)
 __global__ __launch_bounds__(256) void kmeans_assign_kernel(const focal_kmeans_desc d, const float* __restrict__ x, const float* __restrict__ c,
                                                             const float* __restrict__ c_sq, int* __restrict__ labels,
                                                             float* __restrict__ min_d2, int* __restrict__ changed) {
-  using StQ = OperandStage<float, float, false, PRO_NONE, KNN_BQ, 1>;
-  using StT = OperandStage<float, float, false, PRO_NONE, KNN_BT, 1>;
-  using FQ = FragLoad<float, false, StQ::PITCH>;
-  using FT = FragLoad<float, false, StT::PITCH>;
-  static_assert(GemmCfg<float>::BK == KNN_BK, "k-step of the fp32 staging");
-  constexpr int DP = KNN_BT + 4;
-  __shared__ __attribute__((aligned(16))) float lds_q[StQ::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float lds_t[StT::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float d2s[KNN_BQ * DP];
-  __shared__ float qsq_s[KNN_BQ];
+  __shared__ PairTile::Lds lds;
+  constexpr int DP = PairTile::DP;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int D = d.D, K = d.K, RK = d.R * d.K, n = d.n;
   const int q0 = (int)blockIdx.x * KNN_BQ;
   const int q_ext = n - q0;
   const float* qb = x + (long)q0 * D;
 
-  knn_row_norms(qb, D, q_ext, tid, qsq_s);
+  knn_row_norms(qb, D, q_ext, tid, lds.qsq);
 
   // the scan's state: the restart and the centroid within it of the next column, and the best of the restart so far (all but `best` are
   // the same in every thread)
   int cur_r = 0, cur_k = 0;
   unsigned long long best = KNN_EMPTY;
 
-  const int nK = (D + KNN_BK - 1) / KNN_BK, nT = (RK + KNN_BT - 1) / KNN_BT;
-  MaskEval me;  // (PRO_NONE: never read)
-  StQ sq;
-  StT st;
-  sq.init(D, 0, tid);
-  st.init(D, 0, tid);
-  auto load = [&](int ti, int ks) {
-    const int t0 = ti * KNN_BT;
-    sq.load(qb, D, 0, ks * KNN_BK, q_ext, D, tid, me);
-    st.load(c + (long)t0 * D, D, 0, ks * KNN_BK, RK - t0, D, tid, me);  // rows past the last centroid (or a ragged k block) arrive as zeros
-  };
+  const int nT = (RK + KNN_BT - 1) / KNN_BT;
+  PairTile pt(lds, qb, D, q_ext);
+  auto load = [&](int ti, int ks) { pt.load(c, 0, RK, ti, ks); };
   load(0, 0);
   for (int ti = 0; ti < nT; ++ti) {
     f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < nK; ++ks) {
-      sq.template store<false>(lds_q, 0, ks * KNN_BK, tid, me, nullptr);
-      st.template store<false>(lds_t, 0, ks * KNN_BK, tid, me, nullptr);
-      __syncthreads();
-      if (ks + 1 < nK) load(ti, ks + 1);
-      else if (ti + 1 < nT) load(ti + 1, 0);
-#pragma unroll
-      for (int kk = 0; kk < KNN_BK / 4; ++kk) {
-        float xq[2], xt[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xq[i] = FQ::load(lds_q, wave * 32 + i * 16, kk, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xt[j] = FT::load(lds_t, j * 16, kk, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mma16(xq[i], xt[j], acc[i][j]);  // rows (4 (lane >> 4) + reg) = rows of x, column (lane & 15) = centroid
-      }
-      __syncthreads();
-    }
-    // the distance tile, as knn_search_kernel writes it
+    pt.product(acc, ti, nT, load);
     const int t0 = ti * KNN_BT;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int tc = j * 16 + (lane & 15);
-      const float ts = (t0 + tc < RK) ? c_sq[t0 + tc] : 0.f;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int qr = wave * 32 + i * 16 + 4 * (lane >> 4) + r;
-          d2s[qr * DP + tc] = fmaf(-2.0f, acc[i][j][r], qsq_s[qr] + ts);
-        }
-    }
-    __syncthreads();
+    float ts[4];
+    pt.col_norms(ts, c_sq, t0, RK);
+    pt.write_d2(acc, ts);
     if (tid < KNN_BQ) {  // (waves 0 and 1, whole: the ballot below counts a wave's 64 rows)
       const int valid = RK - t0 < KNN_BT ? RK - t0 : KNN_BT;
       const bool live = tid < q_ext;
-      const float4* row = reinterpret_cast<const float4*>(d2s + tid * DP);
+      const float4* row = reinterpret_cast<const float4*>(lds.d2 + tid * DP);
       for (int cc = 0; cc < KNN_BT / 4; ++cc) {
         const float4 v = row[cc];
         const float f[4] = {v.x, v.y, v.z, v.w};

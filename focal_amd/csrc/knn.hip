@@ -1,13 +1,11 @@
 // k-nearest-neighbour search and vote for scoring a pretrained backbone (train_utils/knn.py: GpuKNNClassifier.predict_fused).
 //
 // focal_knn_search: a workgroup owns KNN_BQ = 128 query rows and one of `slices` contiguous slices of the training rows.  It walks the slice
-// in tiles of KNN_BT = 64 rows: the 128 x 64 block of q . t is the exact-fp32 MFMA product (v_mfma_f32_16x16x4_f32) on the fp32 GEMM family's
-// staging (gemm.hpp: OperandStage / FragLoad, one LDS buffer, the next k-step's global loads in registers), d2 = (|q|^2 + |t|^2) - 2 q.t is
-// written to an LDS tile and goes no further: one thread per query row scans its 64 candidates against the last entry of the row's running
-// k-best, which lives in that thread's registers.  An entry is ONE 64-bit word, (order-preserving key of d2) << 32 | training index, so the
-// order (d2, index) is an integer compare, a NaN distance (key 0xFFFFFFFF) orders behind every number, and an empty slot (all ones) behind
-// every candidate.  d2 of a pair is a function of the two rows alone -- the k-ordered fma chain of the MFMA from k = 0, |q|^2 by a fixed
-// tree, |t|^2 passed in -- whatever tile, lane or slice the pair falls into: the result is bit-identical for every `slices`.
+// in tiles of KNN_BT = 64 rows: the 128 x 64 distance tile is knn_dist.hpp's PairTile, written to LDS and no further: one thread per query
+// row scans its 64 candidates against the last entry of the row's running k-best, which lives in that thread's registers.  An entry is ONE
+// 64-bit word, (order-preserving key of d2) << 32 | training index, so the order (d2, index) is an integer compare, a NaN distance (key
+// 0xFFFFFFFF) orders behind every number, and an empty slot (all ones) behind every candidate.  d2 of a pair is a function of the two rows
+// alone (knn_dist.hpp), whatever tile, lane or slice the pair falls into: the result is bit-identical for every `slices`.
 // focal_knn_vote: one thread per query merges the `slices` lists under the same order, votes (most frequent label, ties to the smallest)
 // and optionally writes the neighbour lists and adds to a confusion matrix laid out as focal_eval_accumulate's.
 #include "knn_dist.hpp"
@@ -38,88 +36,36 @@ template <int KC>
 __global__ __launch_bounds__(256) void knn_search_kernel(const focal_knn_desc d, const float* __restrict__ q, const float* __restrict__ t,
                                                          const float* __restrict__ t_sq, float* __restrict__ part_d2,
                                                          int* __restrict__ part_idx) {
-  using StQ = OperandStage<float, float, false, PRO_NONE, KNN_BQ, 1>;
-  using StT = OperandStage<float, float, false, PRO_NONE, KNN_BT, 1>;
-  using FQ = FragLoad<float, false, StQ::PITCH>;
-  using FT = FragLoad<float, false, StT::PITCH>;
-  static_assert(GemmCfg<float>::BK == KNN_BK, "k-step of the fp32 staging");
-  constexpr int DP = KNN_BT + 4;  // pitch of the distance tile (16-byte rows for the scan's ds_read_b128)
-  __shared__ __attribute__((aligned(16))) float lds_q[StQ::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float lds_t[StT::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float d2s[KNN_BQ * DP];
-  __shared__ float qsq_s[KNN_BQ];
+  __shared__ PairTile::Lds lds;
+  constexpr int DP = PairTile::DP;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int D = d.D, k = d.k;
   const int s = (int)(blockIdx.x % (unsigned)d.slices), q0 = (int)(blockIdx.x / (unsigned)d.slices) * KNN_BQ;
-  const long per = ((long)d.nt + d.slices - 1) / d.slices;
-  const long lo_l = (long)s * per < (long)d.nt ? (long)s * per : (long)d.nt;
-  const int lo = (int)lo_l, hi = (int)(lo_l + per < (long)d.nt ? lo_l + per : (long)d.nt);
+  int lo, hi;
+  knn_slice(d.nt, d.slices, s, lo, hi);
   const int q_ext = d.nq - q0;
   const float* qb = q + (long)q0 * D;
 
-  knn_row_norms(qb, D, q_ext, tid, qsq_s);
+  knn_row_norms(qb, D, q_ext, tid, lds.qsq);
 
   KnnBest<KC> best;
   best.init();
 
-  const int nK = (D + KNN_BK - 1) / KNN_BK, nT = (hi - lo + KNN_BT - 1) / KNN_BT;
-  MaskEval me;  // (PRO_NONE: never read)
-  StQ sq;
-  StT st;
-  sq.init(D, 0, tid);
-  st.init(D, 0, tid);
-  auto load = [&](int ti, int ks) {
-    const int t0 = lo + ti * KNN_BT;
-    sq.load(qb, D, 0, ks * KNN_BK, q_ext, D, tid, me);
-    st.load(t + (long)t0 * D, D, 0, ks * KNN_BK, hi - t0, D, tid, me);  // rows past the slice (or a ragged k block) arrive as zeros
-  };
+  const int nT = (hi - lo + KNN_BT - 1) / KNN_BT;
+  PairTile pt(lds, qb, D, q_ext);
+  auto load = [&](int ti, int ks) { pt.load(t, lo, hi, ti, ks); };
   if (nT > 0) load(0, 0);
   for (int ti = 0; ti < nT; ++ti) {
     f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < nK; ++ks) {
-      sq.template store<false>(lds_q, 0, ks * KNN_BK, tid, me, nullptr);
-      st.template store<false>(lds_t, 0, ks * KNN_BK, tid, me, nullptr);
-      __syncthreads();
-      if (ks + 1 < nK) load(ti, ks + 1);
-      else if (ti + 1 < nT) load(ti + 1, 0);
-#pragma unroll
-      for (int kk = 0; kk < KNN_BK / 4; ++kk) {
-        float xq[2], xt[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xq[i] = FQ::load(lds_q, wave * 32 + i * 16, kk, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xt[j] = FT::load(lds_t, j * 16, kk, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mma16(xq[i], xt[j], acc[i][j]);  // rows (4 (lane >> 4) + reg) = queries, column (lane & 15) = training row
-      }
-      __syncthreads();
-    }
-    // the distance tile: written after the k loop's last barrier, read by the scan below; the next tile's k loop has barriers of its own
-    // before anything writes it again
+    pt.product(acc, ti, nT, load);
     const int t0 = lo + ti * KNN_BT;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int tc = j * 16 + (lane & 15);
-      const float ts = (t0 + tc < hi) ? t_sq[t0 + tc] : 0.f;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int qr = wave * 32 + i * 16 + 4 * (lane >> 4) + r;
-          d2s[qr * DP + tc] = fmaf(-2.0f, acc[i][j][r], qsq_s[qr] + ts);
-        }
-    }
-    __syncthreads();
+    float ts[4];
+    pt.col_norms(ts, t_sq, t0, hi);
+    pt.write_d2(acc, ts);
     if (tid < KNN_BQ) {
       const int valid = hi - t0 < KNN_BT ? hi - t0 : KNN_BT;
-      const float4* row = reinterpret_cast<const float4*>(d2s + tid * DP);
+      const float4* row = reinterpret_cast<const float4*>(lds.d2 + tid * DP);
 #pragma unroll 4
       for (int c = 0; c < KNN_BT / 4; ++c) {
         const float4 v = row[c];

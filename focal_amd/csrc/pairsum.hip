@@ -1,9 +1,9 @@
 // Sums of a function of the distance over all pairs, per query row and per group of gallery rows, for the embedding-geometry scores
 // (train_utils/geometry.py: silhouette, uniformity; src/eval_geometry.py).  The [nq, nt] distances exist in LDS tiles only.
 //
-// focal_pair_sums is the tile loop of focal_rank_positive's scan (rank.hip) -- the 128 x 64 exact-fp32 MFMA product of focal_knn_search
-// (knn.hip) on the same staging, the same k order and the same fmaf(-2, acc, |q|^2 + |t|^2), so d2 of a pair is the bits the search
-// produces for it -- with another epilogue, which adds f(max(d2, 0)) of every candidate to the sum of the candidate's group.
+// focal_pair_sums walks slices of t in knn_dist.hpp's PairTile, as focal_rank_positive's scan (rank.hip) does -- d2 of a pair is the bits
+// focal_knn_search produces for it -- with another epilogue, which adds f(max(d2, 0)) of every candidate to the sum of the candidate's
+// group.
 // Where the accumulators live (NB):
 // NB = 0, group == NULL (one group, the uniformity case): two threads per query row scan 32 candidates each of the distance tile, as the
 // rank kernel does, and each keeps ONE register; the halves meet once, half 0 + half 1, through the distance tile after the last tile.
@@ -23,43 +23,27 @@
 
 #include <cmath>
 
-template <int FN>
-__device__ __forceinline__ float pairsum_fn(float d2, float scale) {
-  const float x = d2 < 0.f ? 0.f : d2;  // (a NaN distance stays NaN)
-  if (FN == FOCAL_PAIR_SQDIST) return x;
-  if (FN == FOCAL_PAIR_DIST) return sqrtf(x);
-  return expf(-scale * x);
-}
-
 template <int FN, int NB>
 __global__ __launch_bounds__(256) void pairsum_kernel(const focal_pairsum_desc d, const float* __restrict__ q, const float* __restrict__ t,
                                                       const float* __restrict__ t_sq, const int* __restrict__ group, float* __restrict__ out) {
-  using StQ = OperandStage<float, float, false, PRO_NONE, KNN_BQ, 1>;
-  using StT = OperandStage<float, float, false, PRO_NONE, KNN_BT, 1>;
-  using FQ = FragLoad<float, false, StQ::PITCH>;
-  using FT = FragLoad<float, false, StT::PITCH>;
-  static_assert(GemmCfg<float>::BK == KNN_BK, "k-step of the fp32 staging");
   static_assert(NB * 16 <= FOCAL_PAIR_MAX_GROUPS, "16 groups per block of columns");
-  constexpr int DP = KNN_BT + 4;  // pitch of the distance tile, as in the search
+  constexpr int DP = PairTile::DP;
   constexpr int NBR = NB > 0 ? NB : 1;
-  __shared__ __attribute__((aligned(16))) float lds_q[StQ::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float lds_t[StT::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float d2s[KNN_BQ * DP];
-  __shared__ float qsq_s[KNN_BQ];
+  __shared__ PairTile::Lds lds;
   __shared__ __attribute__((aligned(16))) int grp_s[KNN_BT];  // the tile's group ids, -1 = not counted (NB > 0)
+  float* d2s = lds.d2;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int D = d.D, G = d.G;
   const int s = (int)(blockIdx.x % (unsigned)d.slices);
   const int q_tile = (int)(blockIdx.x / (unsigned)d.slices);
   const int q0 = q_tile * KNN_BQ;
-  const long per = ((long)d.nt + d.slices - 1) / d.slices;
-  const long lo_l = (long)s * per < (long)d.nt ? (long)s * per : (long)d.nt;
+  int lo, hi;
+  knn_slice(d.nt, d.slices, s, lo, hi);
   const int q_ext = d.nq - q0;
-  const int lo = (int)lo_l, hi = (int)(lo_l + per < (long)d.nt ? lo_l + per : (long)d.nt);
   const float* qb = q + (long)q0 * D;
 
-  knn_row_norms(qb, D, q_ext, tid, qsq_s);
+  knn_row_norms(qb, D, q_ext, tid, lds.qsq);
   __syncthreads();
 
   // NB = 0: scan state of thread (row = tid & 127, half = tid >> 7).  NB > 0: the lane's two A rows (wave * 32 + i * 16 + (lane & 15))
@@ -73,73 +57,25 @@ __global__ __launch_bounds__(256) void pairsum_kernel(const focal_pairsum_desc d
 #pragma unroll
     for (int nb = 0; nb < NBR; ++nb) sacc[i][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nK = (D + KNN_BK - 1) / KNN_BK, nT = (hi - lo + KNN_BT - 1) / KNN_BT;
-  MaskEval me;  // (PRO_NONE: never read)
-  StQ sq;
-  StT st;
-  sq.init(D, 0, tid);
-  st.init(D, 0, tid);
-  auto load = [&](int ti, int ks) {
-    const int t0 = lo + ti * KNN_BT;
-    sq.load(qb, D, 0, ks * KNN_BK, q_ext, D, tid, me);
-    st.load(t + (long)t0 * D, D, 0, ks * KNN_BK, hi - t0, D, tid, me);  // rows past the slice (or a ragged k block) arrive as zeros
-  };
+  const int nT = (hi - lo + KNN_BT - 1) / KNN_BT;
+  PairTile pt(lds, qb, D, q_ext);
+  auto load = [&](int ti, int ks) { pt.load(t, lo, hi, ti, ks); };
   if (nT > 0) load(0, 0);
   for (int ti = 0; ti < nT; ++ti) {
-    f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     // the tile's norms and group ids are asked for before the k loop, so that their latency is not paid between the loop and the epilogue
     const int t0 = lo + ti * KNN_BT;
     float ts_pre[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int tc = j * 16 + (lane & 15);
-      ts_pre[j] = t0 + tc < hi ? t_sq[t0 + tc] : 0.f;
-    }
+    pt.col_norms(ts_pre, t_sq, t0, hi);
     int g_pre = -1;
     if (NB > 0 && tid < KNN_BT && t0 + tid < hi) {
       g_pre = group ? group[t0 + tid] : 0;
       if (g_pre < 0 || g_pre >= G) g_pre = -1;
     }
-    for (int ks = 0; ks < nK; ++ks) {
-      sq.template store<false>(lds_q, 0, ks * KNN_BK, tid, me, nullptr);
-      st.template store<false>(lds_t, 0, ks * KNN_BK, tid, me, nullptr);
-      __syncthreads();
-      if (ks + 1 < nK) load(ti, ks + 1);
-      else if (ti + 1 < nT) load(ti + 1, 0);
-#pragma unroll
-      for (int kk = 0; kk < KNN_BK / 4; ++kk) {
-        float xq[2], xt[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xq[i] = FQ::load(lds_q, wave * 32 + i * 16, kk, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xt[j] = FT::load(lds_t, j * 16, kk, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mma16(xq[i], xt[j], acc[i][j]);  // rows (4 (lane >> 4) + reg) = queries, column (lane & 15) = gallery row
-      }
-      __syncthreads();
-    }
-    // the distance tile and its columns' groups: written after the k loop's last barrier, read below; the next tile's k loop has barriers
-    // of its own before anything writes them again
+    f32x4 acc[2][4];
+    pt.product(acc, ti, nT, load);
+    // the columns' groups go with the distance tile: written after the k loop's last barrier, published by write_d2's
     if (NB > 0 && tid < KNN_BT) grp_s[tid] = g_pre;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int tc = j * 16 + (lane & 15);
-      const float ts = ts_pre[j];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int qr = wave * 32 + i * 16 + 4 * (lane >> 4) + r;
-          d2s[qr * DP + tc] = fmaf(-2.0f, acc[i][j][r], qsq_s[qr] + ts);
-        }
-    }
-    __syncthreads();
+    pt.write_d2(acc, ts_pre);
     if (NB > 0) {
       // S tile [32 rows of this wave, 16 NB groups] += F [32, 64] x onehot [64, 16 NB].  The product does not care which candidate is
       // which k as long as A and B agree: lane (row = lane & 15, c = lane >> 4) owns the 16 consecutive candidates 16 c .. 16 c + 15 of
@@ -166,7 +102,7 @@ __global__ __launch_bounds__(256) void pairsum_kernel(const focal_pairsum_desc d
           const int col = c16 + 4 * m + e, g = gs[e];
           float a[2];
 #pragma unroll
-          for (int i = 0; i < 2; ++i) a[i] = (g >= 0 && col != self_col[i]) ? pairsum_fn<FN>(fv[i][e], d.scale) : 0.f;
+          for (int i = 0; i < 2; ++i) a[i] = (g >= 0 && col != self_col[i]) ? pair_fn<FN>(fv[i][e], d.scale) : 0.f;
 #pragma unroll
           for (int nb = 0; nb < NBR; ++nb) {
             const float b = g == nb * 16 + (lane & 15) ? 1.f : 0.f;
@@ -185,7 +121,7 @@ __global__ __launch_bounds__(256) void pairsum_kernel(const focal_pairsum_desc d
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int col = c0 + 4 * c + e;
-          const float term = pairsum_fn<FN>(f[e], d.scale);
+          const float term = pair_fn<FN>(f[e], d.scale);
           sum1 += (col < valid && (long)t0 + col != self_j) ? term : 0.f;
         }
       }
@@ -227,12 +163,10 @@ __global__ __launch_bounds__(256) void pairsum_reduce_kernel(const focal_pairsum
 
 static int pairsum_check_desc(const focal_pairsum_desc* d, const char* who) {
   FOCAL_CHECK_ARG(d, "%s: null descriptor", who);
-  FOCAL_CHECK_ARG(d->D >= 4 && d->D % 4 == 0, "%s: need D >= 4 and D %% 4 == 0 (got D=%d)", who, d->D);
+  const int rc = knn_check_tile_desc(who, d->D, d->slices, d->nq, "nq");
+  if (rc != FOCAL_OK) return rc;
   FOCAL_CHECK_ARG(d->nq >= 1 && d->nt >= 1, "%s: need nq >= 1 and nt >= 1 (got nq=%d nt=%d)", who, d->nq, d->nt);
   FOCAL_CHECK_ARG(d->G >= 1 && d->G <= FOCAL_PAIR_MAX_GROUPS, "%s: need 1 <= G <= %d (got G=%d)", who, FOCAL_PAIR_MAX_GROUPS, d->G);
-  FOCAL_CHECK_ARG(d->slices >= 1 && d->slices <= 65535, "%s: need 1 <= slices <= 65535 (got slices=%d)", who, d->slices);
-  FOCAL_CHECK_ARG((long)ceil_div(d->nq, KNN_BQ) * d->slices < (1L << 31), "%s: nq / %d * slices exceeds the launch grid (nq=%d slices=%d)", who,
-                  KNN_BQ, d->nq, d->slices);
   FOCAL_CHECK_ARG(((long)d->nq * d->G + 255) / 256 < (1L << 31), "%s: nq * G / 256 exceeds the launch grid (nq=%d G=%d)", who, d->nq, d->G);
   FOCAL_CHECK_ARG(d->fn >= FOCAL_PAIR_SQDIST && d->fn <= FOCAL_PAIR_GAUSS, "%s: need fn in 0 .. 2 (sqdist, dist, gauss; got fn=%d)", who, d->fn);
   FOCAL_CHECK_ARG(std::isfinite(d->scale) && d->scale >= 0.f, "%s: need a finite scale >= 0 (got scale=%g)", who, (double)d->scale);

@@ -4,8 +4,8 @@
 // forward, accumulate, finish -- with no floating-point atomic in any of them.
 //
 // focal_probe_forward: kmeans_assign_kernel's product with the centroids replaced by the weight rows.  A workgroup owns KNN_BQ = 128 rows
-// of x and walks ALL R*C weight rows in tiles of KNN_BT = 64: the same exact-fp32 MFMA product on the same staging, z = x.w + b written to
-// an LDS tile and no further.  One thread per row scans the tile's columns in order; column j belongs to problem j / C, so the thread
+// of x and walks ALL R*C weight rows in tiles of KNN_BT = 64: the product of knn_dist.hpp's PairTile, z = x.w + b written to its LDS tile
+// and no further.  One thread per row scans the tile's columns in order; column j belongs to problem j / C, so the thread
 // carries the problem's running (max, sum of exp, z_y, argmax) and closes the problem when the column counter reaches C -- whether or not
 // a tile boundary fell inside it.  The softmax of a closed problem is a second pass over its C logits: those of this tile from LDS, those
 // of the tile before (C <= 64: never more than one) from g, where the same thread parked them when that tile ended.
@@ -24,17 +24,11 @@ constexpr int PG_PITCH = 80;  // LDS pitch of both blocks: 80 % 32 == 16, so the
 __global__ __launch_bounds__(256) void probe_forward_kernel(const focal_probe_desc d, const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ b, const int* __restrict__ y, float* __restrict__ ce,
                                                             float* g, int* __restrict__ preds) {
-  using StQ = OperandStage<float, float, false, PRO_NONE, KNN_BQ, 1>;
-  using StT = OperandStage<float, float, false, PRO_NONE, KNN_BT, 1>;
-  using FQ = FragLoad<float, false, StQ::PITCH>;
-  using FT = FragLoad<float, false, StT::PITCH>;
-  static_assert(GemmCfg<float>::BK == KNN_BK, "k-step of the fp32 staging");
-  constexpr int DP = KNN_BT + 4;
-  __shared__ __attribute__((aligned(16))) float lds_q[StQ::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float lds_t[StT::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float zs[KNN_BQ * DP];
+  __shared__ PairTile::Lds lds;  // (the logits tile is its d2; its qsq is not used)
+  constexpr int DP = PairTile::DP;
+  float* zs = lds.d2;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int D = d.D, C = d.C, RC = d.R * d.C, n = d.n;
   const int q0 = (int)blockIdx.x * KNN_BQ;
   const int q_ext = n - q0;
@@ -48,58 +42,23 @@ __global__ __launch_bounds__(256) void probe_forward_kernel(const focal_probe_de
   float m = NEG_INF, s = 0.f, zy = 0.f, bz = QNAN;
   float* grow = g ? g + (long)(q0 + (live ? tid : 0)) * RC : nullptr;
 
-  const int nK = (D + KNN_BK - 1) / KNN_BK, nT = (RC + KNN_BT - 1) / KNN_BT;
-  MaskEval me;  // (PRO_NONE: never read)
-  StQ sq;
-  StT st;
-  sq.init(D, 0, tid);
-  st.init(D, 0, tid);
-  auto load = [&](int ti, int ks) {
-    const int t0 = ti * KNN_BT;
-    sq.load(qb, D, 0, ks * KNN_BK, q_ext, D, tid, me);
-    st.load(w + (long)t0 * D, D, 0, ks * KNN_BK, RC - t0, D, tid, me);  // rows past the last weight row (or a ragged k block) arrive as zeros
-  };
+  const int nT = (RC + KNN_BT - 1) / KNN_BT;
+  PairTile pt(lds, qb, D, q_ext);
+  auto load = [&](int ti, int ks) { pt.load(w, 0, RC, ti, ks); };
   load(0, 0);
   for (int ti = 0; ti < nT; ++ti) {
     f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < nK; ++ks) {
-      sq.template store<false>(lds_q, 0, ks * KNN_BK, tid, me, nullptr);
-      st.template store<false>(lds_t, 0, ks * KNN_BK, tid, me, nullptr);
-      __syncthreads();
-      if (ks + 1 < nK) load(ti, ks + 1);
-      else if (ti + 1 < nT) load(ti + 1, 0);
-#pragma unroll
-      for (int kk = 0; kk < KNN_BK / 4; ++kk) {
-        float xq[2], xt[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xq[i] = FQ::load(lds_q, wave * 32 + i * 16, kk, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xt[j] = FT::load(lds_t, j * 16, kk, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mma16(xq[i], xt[j], acc[i][j]);  // rows (4 (lane >> 4) + reg) = rows of x, column (lane & 15) = weight row
-      }
-      __syncthreads();
-    }
-    // the logits tile: written after the k loop's last barrier, read by the scan below; the next tile's k loop has barriers of its own
-    // before anything writes it again
+    pt.product(acc, ti, nT, load);
+    // the logits tile, in the place and under the barriers of PairTile::write_d2
     const int t0 = ti * KNN_BT;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int tc = j * 16 + (lane & 15);
+      const int tc = pt.col(j);
       const float bias = (t0 + tc < RC) ? b[t0 + tc] : 0.f;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int qr = wave * 32 + i * 16 + 4 * (lane >> 4) + r;
-          zs[qr * DP + tc] = acc[i][j][r] + bias;
-        }
+        for (int r = 0; r < 4; ++r) zs[pt.row(i, r) * DP + tc] = acc[i][j][r] + bias;
     }
     __syncthreads();
     if (tid < KNN_BQ) {

@@ -1,8 +1,8 @@
 // Rank of one named gallery row per query, for cross-modal retrieval of the projected embeddings (train_utils/retrieval.py:
 // cross_modal_ranks, src/eval_retrieval.py).  The [nq, nt] distances exist in LDS tiles only.
 //
-// focal_rank_positive is two launches of ONE tile loop -- the 128 x 64 exact-fp32 MFMA product of focal_knn_search (knn.hip) on the same
-// staging, the same k order and the same fmaf(-2, acc, |q|^2 + |t|^2), so d2 of a pair is the bits the search produces for it:
+// focal_rank_positive is two launches of ONE tile loop -- knn_dist.hpp's PairTile, so d2 of a pair is the bits focal_knn_search (knn.hip)
+// produces for it:
 // rank_kernel<true>: a workgroup owns 128 queries and runs the product against the GATHERED rows t[pos[q0 .. q0 + 127]] (tiles of 64);
 // the diagonal of each tile is d2(i, pos_i).  Because d2 of a pair does not depend on the tile or lane it falls into, those are the bits
 // the scan sees in column pos_i.  The launch writes pos_d2 and zeroes before / tied (-1 / -1 / NaN for a pos outside [0, nt), whose row is
@@ -16,36 +16,29 @@ template <bool GATHER>
 __global__ __launch_bounds__(256) void rank_kernel(const focal_rank_desc d, const float* __restrict__ q, const float* __restrict__ t,
                                                    const float* __restrict__ t_sq, const int* __restrict__ pos, int* __restrict__ before,
                                                    int* __restrict__ tied, float* __restrict__ pos_d2) {
-  using StQ = OperandStage<float, float, false, PRO_NONE, KNN_BQ, 1>;
-  using StT = OperandStage<float, float, false, PRO_NONE, KNN_BT, 1>;
-  using FQ = FragLoad<float, false, StQ::PITCH>;
-  using FT = FragLoad<float, false, StT::PITCH>;
-  static_assert(GemmCfg<float>::BK == KNN_BK, "k-step of the fp32 staging");
+  using StT = PairTile::StT;
   static_assert(StT::NCH == 2 && StT::CPR == 8, "the gather below addresses the training stage's chunks");
-  constexpr int DP = KNN_BT + 4;  // pitch of the distance tile, as in the search
-  __shared__ __attribute__((aligned(16))) float lds_q[StQ::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float lds_t[StT::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float d2s[KNN_BQ * DP];
-  __shared__ float qsq_s[KNN_BQ];
+  constexpr int DP = PairTile::DP;
+  __shared__ PairTile::Lds lds;
+  float* d2s = lds.d2;
   // the rows' positives, -1 where there is none (row past nq, or pos outside [0, nt)), live in the distance tile's first pad column, which
   // no distance is written to: the footprint is the search's
   auto pos_of = [&](int row) -> int& { return reinterpret_cast<int*>(d2s)[row * DP + KNN_BT]; };
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int D = d.D;
-  const int s = GATHER ? 0 : (int)(blockIdx.x % (unsigned)d.slices);
   const int q0 = (GATHER ? (int)blockIdx.x : (int)(blockIdx.x / (unsigned)d.slices)) * KNN_BQ;
-  const long per = ((long)d.nt + d.slices - 1) / d.slices;
-  const long lo_l = (long)s * per < (long)d.nt ? (long)s * per : (long)d.nt;
   const int q_ext = d.nq - q0;
-  const int lo = GATHER ? 0 : (int)lo_l, hi = GATHER ? (q_ext < KNN_BQ ? q_ext : KNN_BQ) : (int)(lo_l + per < (long)d.nt ? lo_l + per : (long)d.nt);
+  // GATHER: the gathered rows 0 .. (the workgroup's queries) - 1; else slice blockIdx.x % slices of t
+  int lo = 0, hi = q_ext < KNN_BQ ? q_ext : KNN_BQ;
+  if (!GATHER) knn_slice(d.nt, d.slices, (int)(blockIdx.x % (unsigned)d.slices), lo, hi);
   const float* qb = q + (long)q0 * D;
 
   if (tid < KNN_BQ) {
     const int p = tid < q_ext ? pos[q0 + tid] : -1;
     pos_of(tid) = (p >= 0 && p < d.nt) ? p : -1;
   }
-  knn_row_norms(qb, D, q_ext, tid, qsq_s);
+  knn_row_norms(qb, D, q_ext, tid, lds.qsq);
   __syncthreads();
 
   // scan state of thread (row = tid & 127, half = tid >> 7): the positive's key and index, and the two counters
@@ -55,77 +48,40 @@ __global__ __launch_bounds__(256) void rank_kernel(const focal_rank_desc d, cons
   int n_before = 0, n_tied = 0;
   if (!GATHER && my_p >= 0) my_key = knn_key(pos_d2[q0 + srow]);
 
-  const int nK = (D + KNN_BK - 1) / KNN_BK, nT = (hi - lo + KNN_BT - 1) / KNN_BT;
-  MaskEval me;  // (PRO_NONE: never read)
-  StQ sq;
-  StT st;
-  sq.init(D, 0, tid);
-  st.init(D, 0, tid);
+  const int nT = (hi - lo + KNN_BT - 1) / KNN_BT;
+  PairTile pt(lds, qb, D, q_ext);
   auto load = [&](int ti, int ks) {
-    const int t0 = lo + ti * KNN_BT;
-    sq.load(qb, D, 0, ks * KNN_BK, q_ext, D, tid, me);
-    if (GATHER) {
-      // chunk j of this thread is 16 bytes of gathered row t0 + a: the row pos names, or zeros where it names none
+    if (!GATHER) {
+      pt.load(t, lo, hi, ti, ks);
+      return;
+    }
+    // chunk j of this thread is 16 bytes of gathered row t0 + a: the row pos names, or zeros where it names none
+    const int t0 = ti * KNN_BT;
+    pt.load_q(ks);
 #pragma unroll
-      for (int j = 0; j < StT::NCH; ++j) {
-        const int c = tid + 256 * j, a = c / StT::CPR, b = (c % StT::CPR) * StT::EC;
-        const int p = pos_of(t0 + a), r = ks * KNN_BK + b;
-        const bool ok = p >= 0 && r < D;
-        raw_load(st.raw[j], t + (ok ? (long)p * D + r : 0L), ok);
-      }
-    } else {
-      st.load(t + (long)t0 * D, D, 0, ks * KNN_BK, hi - t0, D, tid, me);  // rows past the slice (or a ragged k block) arrive as zeros
+    for (int j = 0; j < StT::NCH; ++j) {
+      const int c = tid + 256 * j, a = c / StT::CPR, b = (c % StT::CPR) * StT::EC;
+      const int p = pos_of(t0 + a), r = ks * KNN_BK + b;
+      const bool ok = p >= 0 && r < D;
+      raw_load(pt.st.raw[j], t + (ok ? (long)p * D + r : 0L), ok);
     }
   };
   if (nT > 0) load(0, 0);
   for (int ti = 0; ti < nT; ++ti) {
     f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < nK; ++ks) {
-      sq.template store<false>(lds_q, 0, ks * KNN_BK, tid, me, nullptr);
-      st.template store<false>(lds_t, 0, ks * KNN_BK, tid, me, nullptr);
-      __syncthreads();
-      if (ks + 1 < nK) load(ti, ks + 1);
-      else if (ti + 1 < nT) load(ti + 1, 0);
-#pragma unroll
-      for (int kk = 0; kk < KNN_BK / 4; ++kk) {
-        float xq[2], xt[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xq[i] = FQ::load(lds_q, wave * 32 + i * 16, kk, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xt[j] = FT::load(lds_t, j * 16, kk, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mma16(xq[i], xt[j], acc[i][j]);  // rows (4 (lane >> 4) + reg) = queries, column (lane & 15) = training row
-      }
-      __syncthreads();
-    }
-    // the distance tile: written after the k loop's last barrier, read below; the next tile's k loop has barriers of its own before
-    // anything writes it again
+    pt.product(acc, ti, nT, load);
     const int t0 = lo + ti * KNN_BT;
+    float ts[4];
+    if (GATHER) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int tc = j * 16 + (lane & 15);
-      float ts = 0.f;
-      if (GATHER) {
-        const int p = pos_of(t0 + tc);
-        if (p >= 0) ts = t_sq[p];
-      } else if (t0 + tc < hi) {
-        ts = t_sq[t0 + tc];
+      for (int j = 0; j < 4; ++j) {
+        const int p = pos_of(t0 + pt.col(j));
+        ts[j] = p >= 0 ? t_sq[p] : 0.f;
       }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int qr = wave * 32 + i * 16 + 4 * (lane >> 4) + r;
-          d2s[qr * DP + tc] = fmaf(-2.0f, acc[i][j][r], qsq_s[qr] + ts);
-        }
+    } else {
+      pt.col_norms(ts, t_sq, t0, hi);
     }
-    __syncthreads();
+    pt.write_d2(acc, ts);
     if (GATHER) {
       // the diagonal: query row t0 + c against gathered row t0 + c
       if (tid < KNN_BT && t0 + tid < q_ext) {
@@ -164,11 +120,9 @@ __global__ __launch_bounds__(256) void rank_kernel(const focal_rank_desc d, cons
 
 static int rank_check_desc(const focal_rank_desc* d, const char* who) {
   FOCAL_CHECK_ARG(d, "%s: null descriptor", who);
-  FOCAL_CHECK_ARG(d->D >= 4 && d->D % 4 == 0, "%s: need D >= 4 and D %% 4 == 0 (got D=%d)", who, d->D);
+  const int rc = knn_check_tile_desc(who, d->D, d->slices, d->nq, "nq");
+  if (rc != FOCAL_OK) return rc;
   FOCAL_CHECK_ARG(d->nq >= 1 && d->nt >= 1, "%s: need nq >= 1 and nt >= 1 (got nq=%d nt=%d)", who, d->nq, d->nt);
-  FOCAL_CHECK_ARG(d->slices >= 1 && d->slices <= 65535, "%s: need 1 <= slices <= 65535 (got slices=%d)", who, d->slices);
-  FOCAL_CHECK_ARG((long)ceil_div(d->nq, KNN_BQ) * d->slices < (1L << 31), "%s: nq / %d * slices exceeds the launch grid (nq=%d slices=%d)", who,
-                  KNN_BQ, d->nq, d->slices);
   return FOCAL_OK;
 }
 

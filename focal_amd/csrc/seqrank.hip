@@ -2,9 +2,8 @@
 // sequence_ranking; src/eval_temporal.py).  Rows a L .. a L + L - 1 of z are sequence a; the [S, S] matrix of pooled distances
 // P(a, b) = sum_{i in a, j in b} f(max(d2(i, j), 0)) exists as L x L blocks of LDS distance tiles only.
 //
-// focal_seq_rank is the tile loop of focal_rank_positive's scan (rank.hip) -- the 128 x 64 exact-fp32 MFMA product of focal_knn_search
-// (knn.hip) on the same staging, the same k order and the same fmaf(-2, acc, |q|^2 + |t|^2), so d2 of a pair is the bits the search
-// produces for it -- with another epilogue, in three launches:
+// focal_seq_rank walks z in knn_dist.hpp's PairTile, as focal_rank_positive's scan (rank.hip) does -- d2 of a pair is the bits
+// focal_knn_search produces for it -- with another epilogue, in three launches:
 // seqrank_kernel<FN, L, true>: a workgroup owns 128 rows and runs the product against ITS OWN rows (two tiles of 64); the L x L blocks on
 // the diagonal are the sequences' own distances.  Because d2 of a pair does not depend on the tile or lane it falls into, those are the
 // bits the scan sees.  The launch writes intra_d2 and intra_sum (one thread per sequence, row-major, i != j) and zeroes before / viol.
@@ -30,31 +29,19 @@
 
 #include <cmath>
 
-template <int FN>
-__device__ __forceinline__ float seqrank_fn(float d2) {
-  const float x = d2 < 0.f ? 0.f : d2;  // (a NaN distance stays NaN)
-  return FN == FOCAL_PAIR_SQDIST ? x : sqrtf(x);
-}
-
 template <int FN, int L, bool INTRA>
 __global__ __launch_bounds__(256) void seqrank_kernel(const focal_seqrank_desc d, const float* __restrict__ z, const float* __restrict__ z_sq,
                                                       float* __restrict__ intra_d2, float* __restrict__ intra_sum, int* __restrict__ before,
                                                       int* __restrict__ viol, float* __restrict__ part_hinge, float* __restrict__ part_inter) {
-  using StQ = OperandStage<float, float, false, PRO_NONE, KNN_BQ, 1>;
-  using StT = OperandStage<float, float, false, PRO_NONE, KNN_BT, 1>;
-  using FQ = FragLoad<float, false, StQ::PITCH>;
-  using FT = FragLoad<float, false, StT::PITCH>;
-  static_assert(GemmCfg<float>::BK == KNN_BK, "k-step of the fp32 staging");
   static_assert(L == 2 || L == 4 || L == 8 || L == 16, "blocks never straddle a tile");
-  constexpr int DP = KNN_BT + 4;    // pitch of the distance tile, as in the search
+  static_assert(FN == FOCAL_PAIR_SQDIST || FN == FOCAL_PAIR_DIST, "pair_fn without a scale");
+  constexpr int DP = PairTile::DP;
   constexpr int NRS = KNN_BQ / L;   // row sequences of a workgroup
   constexpr int TPS = 2 * L;        // threads per row sequence
   constexpr int NBT = KNN_BT / L;   // blocks of a tile per row sequence
   constexpr float L2 = (float)(L * L), L2L = (float)(L * L - L);
-  __shared__ __attribute__((aligned(16))) float lds_q[StQ::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float lds_t[StT::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float d2s[KNN_BQ * DP];
-  __shared__ float qsq_s[KNN_BQ];
+  __shared__ PairTile::Lds lds;
+  float* d2s = lds.d2;
   static_assert(KNN_BQ * DP >= 4 * 256, "the join uses the distance tile");
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -70,7 +57,7 @@ __global__ __launch_bounds__(256) void seqrank_kernel(const focal_seqrank_desc d
   const int hi = INTRA ? q0 + (q_ext < KNN_BQ ? q_ext : KNN_BQ) : (int)(lo_l + per < (long)n ? lo_l + per : (long)n);
   const float* qb = z + (long)q0 * D;
 
-  knn_row_norms(qb, D, q_ext, tid, qsq_s);
+  knn_row_norms(qb, D, q_ext, tid, lds.qsq);
   __syncthreads();
 
   // scan state: virtual thread vt (the ds_read_b128 lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32) made consecutive),
@@ -93,66 +80,18 @@ __global__ __launch_bounds__(256) void seqrank_kernel(const focal_seqrank_desc d
   int n_before = 0, n_viol = 0;
   float s_hinge = 0.f, s_inter = 0.f;
 
-  const int nK = (D + KNN_BK - 1) / KNN_BK, nT = (hi - lo + KNN_BT - 1) / KNN_BT;
-  MaskEval me;  // (PRO_NONE: never read)
-  StQ sq;
-  StT st;
-  sq.init(D, 0, tid);
-  st.init(D, 0, tid);
-  auto load = [&](int ti, int ks) {
-    const int t0 = lo + ti * KNN_BT;
-    sq.load(qb, D, 0, ks * KNN_BK, q_ext, D, tid, me);
-    st.load(z + (long)t0 * D, D, 0, ks * KNN_BK, hi - t0, D, tid, me);  // rows past the slice (or a ragged k block) arrive as zeros
-  };
+  const int nT = (hi - lo + KNN_BT - 1) / KNN_BT;
+  PairTile pt(lds, qb, D, q_ext);
+  auto load = [&](int ti, int ks) { pt.load(z, lo, hi, ti, ks); };
   if (nT > 0) load(0, 0);
   for (int ti = 0; ti < nT; ++ti) {
-    f32x4 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // the tile's norms are asked for before the k loop, so that their latency is not paid between the loop and the epilogue
     const int t0 = lo + ti * KNN_BT;
     float ts_pre[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int tc = j * 16 + (lane & 15);
-      ts_pre[j] = t0 + tc < hi ? z_sq[t0 + tc] : 0.f;
-    }
-    for (int ks = 0; ks < nK; ++ks) {
-      sq.template store<false>(lds_q, 0, ks * KNN_BK, tid, me, nullptr);
-      st.template store<false>(lds_t, 0, ks * KNN_BK, tid, me, nullptr);
-      __syncthreads();
-      if (ks + 1 < nK) load(ti, ks + 1);
-      else if (ti + 1 < nT) load(ti + 1, 0);
-#pragma unroll
-      for (int kk = 0; kk < KNN_BK / 4; ++kk) {
-        float xq[2], xt[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) xq[i] = FQ::load(lds_q, wave * 32 + i * 16, kk, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xt[j] = FT::load(lds_t, j * 16, kk, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = mma16(xq[i], xt[j], acc[i][j]);  // rows (4 (lane >> 4) + reg) = queries, column (lane & 15) = gallery row
-      }
-      __syncthreads();
-    }
-    // the distance tile: written after the k loop's last barrier, read below; the next tile's k loop has barriers of its own before
-    // anything writes it again
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int tc = j * 16 + (lane & 15);
-      const float ts = ts_pre[j];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int qr = wave * 32 + i * 16 + 4 * (lane >> 4) + r;
-          d2s[qr * DP + tc] = fmaf(-2.0f, acc[i][j][r], qsq_s[qr] + ts);
-        }
-    }
-    __syncthreads();
+    pt.col_norms(ts_pre, z_sq, t0, hi);
+    f32x4 acc[2][4];
+    pt.product(acc, ti, nT, load);
+    pt.write_d2(acc, ts_pre);
     if (INTRA) {
       // tile ti holds the own blocks of query rows 64 ti .. 64 ti + 63: block column = block row
       const int r0 = ti * KNN_BT;
@@ -164,7 +103,7 @@ __global__ __launch_bounds__(256) void seqrank_kernel(const focal_seqrank_desc d
         float sum = 0.f;
         for (int i = 0; i < L; ++i)
           for (int j = 0; j < L; ++j)
-            if (i != j) sum += seqrank_fn<FN>(d2s[(r0 + tid * L + i) * DP + tid * L + j]);
+            if (i != j) sum += pair_fn<FN>(d2s[(r0 + tid * L + i) * DP + tid * L + j]);
         const int a = (q0 + r0) / L + tid;
         intra_sum[a] = sum;
         before[a] = 0;
@@ -191,8 +130,8 @@ __global__ __launch_bounds__(256) void seqrank_kernel(const focal_seqrank_desc d
           const float4 v0 = *reinterpret_cast<const float4*>(d2s + (rs * 2) * DP + 4 * bp);
           const float4 v1 = *reinterpret_cast<const float4*>(d2s + (rs * 2 + 1) * DP + 4 * bp);
           float Pa = 0.f, Pb = 0.f;
-          Pa += seqrank_fn<FN>(v0.x); Pa += seqrank_fn<FN>(v0.y); Pa += seqrank_fn<FN>(v1.x); Pa += seqrank_fn<FN>(v1.y);
-          Pb += seqrank_fn<FN>(v0.z); Pb += seqrank_fn<FN>(v0.w); Pb += seqrank_fn<FN>(v1.z); Pb += seqrank_fn<FN>(v1.w);
+          Pa += pair_fn<FN>(v0.x); Pa += pair_fn<FN>(v0.y); Pa += pair_fn<FN>(v1.x); Pa += pair_fn<FN>(v1.y);
+          Pb += pair_fn<FN>(v0.z); Pb += pair_fn<FN>(v0.w); Pb += pair_fn<FN>(v1.z); Pb += pair_fn<FN>(v1.w);
           take(Pa, 2 * bp);
           take(Pb, 2 * bp + 1);
         }
@@ -208,7 +147,7 @@ __global__ __launch_bounds__(256) void seqrank_kernel(const focal_seqrank_desc d
 #pragma unroll
               for (int c = 0; c < L / 4; ++c) {
                 const float4 v = row[c];
-                P += seqrank_fn<FN>(v.x); P += seqrank_fn<FN>(v.y); P += seqrank_fn<FN>(v.z); P += seqrank_fn<FN>(v.w);
+                P += pair_fn<FN>(v.x); P += pair_fn<FN>(v.y); P += pair_fn<FN>(v.z); P += pair_fn<FN>(v.w);
               }
             }
             take(P, b);
@@ -267,13 +206,11 @@ __global__ __launch_bounds__(256) void seqrank_reduce_kernel(const focal_seqrank
 
 static int seqrank_check_desc(const focal_seqrank_desc* d, const char* who) {
   FOCAL_CHECK_ARG(d, "%s: null descriptor", who);
-  FOCAL_CHECK_ARG(d->D >= 4 && d->D % 4 == 0, "%s: need D >= 4 and D %% 4 == 0 (got D=%d)", who, d->D);
+  const int rc = knn_check_tile_desc(who, d->D, d->slices, d->n, "n");
+  if (rc != FOCAL_OK) return rc;
   FOCAL_CHECK_ARG(d->L == 2 || d->L == 4 || d->L == 8 || d->L == 16, "%s: need L in {2, 4, 8, 16} (got L=%d)", who, d->L);
   FOCAL_CHECK_ARG(d->n >= 1 && d->n % d->L == 0, "%s: need n %% L == 0 (got n=%d L=%d)", who, d->n, d->L);
   FOCAL_CHECK_ARG(d->n / d->L >= 2, "%s: need S = n / L >= 2 sequences (got n=%d L=%d)", who, d->n, d->L);
-  FOCAL_CHECK_ARG(d->slices >= 1 && d->slices <= 65535, "%s: need 1 <= slices <= 65535 (got slices=%d)", who, d->slices);
-  FOCAL_CHECK_ARG((long)ceil_div(d->n, KNN_BQ) * d->slices < (1L << 31), "%s: n / %d * slices exceeds the launch grid (n=%d slices=%d)", who,
-                  KNN_BQ, d->n, d->slices);
   FOCAL_CHECK_ARG(d->fn == FOCAL_PAIR_SQDIST || d->fn == FOCAL_PAIR_DIST, "%s: need fn in 0 .. 1 (sqdist, dist; got fn=%d)", who, d->fn);
   FOCAL_CHECK_ARG(std::isfinite(d->margin), "%s: need a finite margin (got margin=%g)", who, (double)d->margin);
   return FOCAL_OK;

@@ -2,9 +2,8 @@
 // is built once by three setup exports; one gradient-descent iteration is two launches -- focal_tsne_grad + focal_tsne_step -- that read P
 // once, make no [n, n] temporary, use no floating-point atomic and read nothing on the host.
 //
-// focal_tsne_dist: d2 [n, n] by the knn_dist.hpp product -- tile (128 rows x 64 columns) of the exact-fp32 MFMA on the fp32 GEMM family's
-// staging, |x_i|^2 by knn_row_norms, |x_j|^2 from the vector the first launch filled with the same tree -- so d2[i, j] is the function of
-// the two rows that focal_knn_search and focal_kmeans_assign compute.  The diagonal is written as +0.
+// focal_tsne_dist: d2 [n, n] by knn_dist.hpp's PairTile, one tile (128 rows x 64 columns) per workgroup; |x_j|^2 from the vector the first
+// launch filled with knn_row_norms' tree, so d2[i, j] is the bits focal_knn_search computes for the pair.  The diagonal is written as +0.
 // focal_tsne_perplexity: one workgroup per row, the row's distances minus their off-diagonal minimum in LDS (n <= 32 768: 128 KiB).  64
 // steps on beta, never fewer: double while no upper bound exists, bisect after; every thread carries the same (lo, beta, hi) because every
 // thread adds the waves' sums in the same order.  The conditional row replaces the distances.
@@ -41,80 +40,30 @@ __global__ __launch_bounds__(256) void tsne_norms_kernel(const focal_tsne_desc d
 // grid (column tiles of 64, row tiles of 128)
 __global__ __launch_bounds__(256) void tsne_dist_kernel(const focal_tsne_desc d, const float* __restrict__ x, const float* __restrict__ x_sq,
                                                         float* __restrict__ d2) {
-  using StQ = OperandStage<float, float, false, PRO_NONE, KNN_BQ, 1>;
-  using StT = OperandStage<float, float, false, PRO_NONE, KNN_BT, 1>;
-  using FQ = FragLoad<float, false, StQ::PITCH>;
-  using FT = FragLoad<float, false, StT::PITCH>;
-  static_assert(GemmCfg<float>::BK == KNN_BK, "k-step of the fp32 staging");
-  constexpr int DP = KNN_BT + 4;
-  __shared__ __attribute__((aligned(16))) float lds_q[StQ::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float lds_t[StT::LDS_ELEMS];
-  __shared__ __attribute__((aligned(16))) float d2s[KNN_BQ * DP];
-  __shared__ float qsq_s[KNN_BQ];
+  __shared__ PairTile::Lds lds;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int D = d.D, n = d.n;
   const int t0 = (int)blockIdx.x * KNN_BT, q0 = (int)blockIdx.y * KNN_BQ;
   const int q_ext = n - q0, t_ext = n - t0;
   const float* qb = x + (long)q0 * D;
-  const float* tb = x + (long)t0 * D;
 
-  knn_row_norms(qb, D, q_ext, tid, qsq_s);
+  knn_row_norms(qb, D, q_ext, tid, lds.qsq);
 
-  const int nK = (D + KNN_BK - 1) / KNN_BK;
-  MaskEval me;  // (PRO_NONE: never read)
-  StQ sq;
-  StT st;
-  sq.init(D, 0, tid);
-  st.init(D, 0, tid);
-  auto load = [&](int ks) {
-    sq.load(qb, D, 0, ks * KNN_BK, q_ext, D, tid, me);
-    st.load(tb, D, 0, ks * KNN_BK, t_ext, D, tid, me);  // rows past the last one (or a ragged k block) arrive as zeros
-  };
-  load(0);
+  // the one tile of this workgroup: tile 0 of the rows t0 .. n - 1
+  PairTile pt(lds, qb, D, q_ext);
+  auto load = [&](int ti, int ks) { pt.load(x, t0, n, ti, ks); };
+  load(0, 0);
   f32x4 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int ks = 0; ks < nK; ++ks) {
-    sq.template store<false>(lds_q, 0, ks * KNN_BK, tid, me, nullptr);
-    st.template store<false>(lds_t, 0, ks * KNN_BK, tid, me, nullptr);
-    __syncthreads();
-    if (ks + 1 < nK) load(ks + 1);
-#pragma unroll
-    for (int kk = 0; kk < KNN_BK / 4; ++kk) {
-      float xq[2], xt[4];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) xq[i] = FQ::load(lds_q, wave * 32 + i * 16, kk, lane);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) xt[j] = FT::load(lds_t, j * 16, kk, lane);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mma16(xq[i], xt[j], acc[i][j]);
-    }
-    __syncthreads();
-  }
-  // the distance tile, as knn_search_kernel writes it
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int tc = j * 16 + (lane & 15);
-    const float ts = tc < t_ext ? x_sq[t0 + tc] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int qr = wave * 32 + i * 16 + 4 * (lane >> 4) + r;
-        d2s[qr * DP + tc] = fmaf(-2.0f, acc[i][j][r], qsq_s[qr] + ts);
-      }
-  }
-  __syncthreads();
+  pt.product(acc, 0, 1, load);
+  float ts[4];
+  pt.col_norms(ts, x_sq, t0, n);
+  pt.write_d2(acc, ts);
   // rows of 64 columns leave coalesced: wave w takes rows w, w + 4, ..
   if (lane < t_ext)
     for (int r = wave; r < KNN_BQ && r < q_ext; r += 4) {
       const int gi = q0 + r, gj = t0 + lane;
-      d2[(long)gi * n + gj] = gi == gj ? 0.f : d2s[r * DP + lane];
+      d2[(long)gi * n + gj] = gi == gj ? 0.f : lds.d2[r * PairTile::DP + lane];
     }
 }
 
@@ -449,9 +398,9 @@ __global__ __launch_bounds__(TS_STEP_THREADS) void tsne_step_kernel(const TsStep
 // ------------------------------------------------------------------------------------------------ exports
 static int tsne_check_desc(const focal_tsne_desc* d, const char* who) {
   FOCAL_CHECK_ARG(d, "%s: null descriptor", who);
-  FOCAL_CHECK_ARG(d->D >= 4 && d->D % 4 == 0, "%s: need D >= 4 and D %% 4 == 0 (got D=%d)", who, d->D);
+  const int rc = knn_check_tile_desc(who, d->D, d->slices, d->n, "n");  // (its grid bound holds for every n <= TSNE_MAX_N)
+  if (rc != FOCAL_OK) return rc;
   FOCAL_CHECK_ARG(d->n >= 2 && d->n <= TSNE_MAX_N, "%s: need 2 <= n <= %d (got n=%d)", who, TSNE_MAX_N, d->n);
-  FOCAL_CHECK_ARG(d->slices >= 1 && d->slices <= 65535, "%s: need 1 <= slices <= 65535 (got slices=%d)", who, d->slices);
   return FOCAL_OK;
 }
 
