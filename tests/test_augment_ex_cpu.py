@@ -44,9 +44,8 @@ def restated_noise(key, salt, shape):
     return torch.from_numpy(z.reshape(shape))
 
 
-def restate(x, scale=1.0, flip=False, perm=None, phase=0.0, noise=None, chan=None, time_mask=None, freq_mask=None):
-    """float64 [B, 2C, I, n] view of x [B, C, I, n]: mask_t(perm / flip / chan-select(scale * x) + noise), the two-sided DFT packed as
-    (Re, Im) channel pairs, the rotation, mask_f.  noise: the tensor ADDED (already times std), or None."""
+def restate_time(x, scale=1.0, flip=False, perm=None, noise=None, chan=None, time_mask=None):
+    """The time-domain half of `restate`: float64 [B, C, I, n] rows as they enter the transform."""
     t = x.double() * scale
     if chan is not None:
         t = t[:, list(chan)]
@@ -59,6 +58,13 @@ def restate(x, scale=1.0, flip=False, perm=None, phase=0.0, noise=None, chan=Non
     if time_mask is not None and time_mask[1] > 0:
         t = t.clone()
         t[..., time_mask[0]:time_mask[0] + time_mask[1]] = 0
+    return t
+
+
+def restate(x, scale=1.0, flip=False, perm=None, phase=0.0, noise=None, chan=None, time_mask=None, freq_mask=None):
+    """float64 [B, 2C, I, n] view of x [B, C, I, n]: mask_t(perm / flip / chan-select(scale * x) + noise), the two-sided DFT packed as
+    (Re, Im) channel pairs, the rotation, mask_f.  noise: the tensor ADDED (already times std), or None."""
+    t = restate_time(x, scale, flip, perm, noise, chan, time_mask)
     f = torch.fft.fft(t, dim=-1) * complex(math.cos(phase), math.sin(phase))
     B, Cc, I, n = t.shape
     out = torch.view_as_real(f).permute(0, 1, 4, 2, 3).reshape(B, 2 * Cc, I, n).clone()
