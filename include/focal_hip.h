@@ -309,6 +309,8 @@ int focal_ape_add_fwd(int N, int cols, float* x, const float* ape, void* stream)
  * nn.LayerNorm(eps 1e-5) of models/SwinModules.py:253,258,376.  x fp32 [rows, C]; y `dtype`; stats fp32
  * [rows, 2] = {mean, rstd}.  gather = 1 is PatchMerging's 2x2 gather fused in front of its LayerNorm
  * (SwinModules.py:388-399): x is [B, H, W, Cin], rows = B*(H/2)*(W/2), C = 4*Cin.
+ * Accepted widths: C a power of two in [16, 1024]; any other C is refused (FOCAL_EINVAL) before a launch.
+ * Gather rule: with gather = 1 the descriptor must satisfy Cin*4 == C, H and W even, rows == B*(H/2)*(W/2) and Cin % 4 == 0, else refused.
  * Backward: dx (fp32) += or = the input gradient (scattered back to [B, H, W, Cin] when gather = 1);
  * dgamma / dbeta (fp32 [C]) are accumulated (+=).
  * dx_masked / mask (both optional): additionally writes dtype(dx * mask) -- dx being the COMPLETED residual-stream
